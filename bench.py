@@ -36,6 +36,15 @@ one-run-per-step timing, simulation inside the graph):
   euro1_cpu   European call, 1-step GBM, 2^14 (>= 10k) paths, CPU torch backend (plumbing)
 Per-GPU path counts are the 8-GPU configs divided by 8 (weak scaling), so a
 1-GPU run measures exactly the per-GPU shard of the 8-GPU job.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line (the headline figure, the configuration and what the last step computed:
+V0, holdings, P&L / residual spread).  ``--full`` adds the records that take
+work of their own: the closed-form price and the analytic hedge on the same
+paths (``quality.anchor`` / ``quality.hedge_anchor``), LM fit statistics
+(``lm``), exchange volume (``lm_exchange``), memory footprint (``memory``) and
+path-samples/s.  ``--dump-outputs DIR`` writes the last step's outputs as
+``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -214,6 +223,11 @@ def parse(argv=None):
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--cpu", action="store_true", help="torch reference backend (plumbing only)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the analytic price / hedge anchors on "
+                         "the same paths, LM fit statistics, exchange volume, memory footprint, path-samples/s")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy")
     ap.add_argument("--seed", type=int, default=1234, help="weight-init seed (the reference's 1234)")
     ap.add_argument("--init", default=None, choices=["reference", "spread", "aligned"],
                     help="weight init (default: preset); aligned = spread + first layer along the basket weights")
@@ -414,6 +428,50 @@ def multistart_record(run, a, world: int) -> dict:
     return rec
 
 
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: budget of the sampled per-path values (the whole dump stays < 64 MB)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, run, res) -> dict:
+    """--dump-outputs: what the last timed step left for a caller of the run
+    (``HedgeRun.collect()``), as float32 / float64 ``.npy`` files of this rank:
+
+      values.npy        [dates + 1, sample] fp32: the portfolio value V_t of every date on a
+                        fixed, seeded sample of this rank's paths (all of them when they fit)
+      values_index.npy  [sample] fp64: the sampled paths' local indices
+      weights.npy       [dates, 2, net floats] fp32: the fitted networks of every date
+      date_stats.npy    [dates, eval stats] fp64: the per-date evaluation sums (t = dates-1 .. 0)
+      pnl_stats.npy     [eval stats] fp64: the self-financing P&L sums
+      summary.npy       [8] fp64: V0, phi0, psi0, terminal P&L std / mean, terminal residual
+                        std / mean, mean discounted payoff
+
+    The paths are Sobol points and the weights start from ``--seed``, so the
+    same arguments give the same inputs in every run and build."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    ind = res.induction
+    vals = ind.values
+    nc, n = int(vals.shape[0]), int(vals.shape[1])
+    ns = min(n, max(1, DUMP_MAX_BYTES // (4 * nc)))
+    idx = np.arange(n) if ns == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, ns, replace=False))
+    sel = torch.from_numpy(idx).to(vals.device)
+    files = {
+        "values": vals.index_select(1, sel).float().cpu().numpy(),
+        "values_index": idx.astype(np.float64),
+        "weights": ind.weights_snapshots.float().cpu().numpy(),
+        "date_stats": np.stack([np.asarray(d.stats, np.float64) for d in ind.dates]),
+        "summary": np.asarray([res.v0, res.phi, res.psi, res.terminal_pnl["std"], res.terminal_pnl["mean"],
+                               res.terminal_residual["std"], res.terminal_residual["mean"],
+                               res.summary["E_payoff"] * run.scale * math.exp(-run.cfg.r * run.cfg.T)], np.float64),
+    }
+    if ind.pnl is not None:
+        files["pnl_stats"] = np.asarray(ind.pnl.stats, np.float64)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in files.items()}
+
+
 def main(argv=None):
     a = parse(argv)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -476,31 +534,9 @@ def main(argv=None):
         dt = D.all_reduce_scalar(dt, op="max", device=run.device)
     res = run.collect()
     ms = 1000.0 * dt / max(a.steps, 1)
-    lm_stats = lm_fit_stats(res.induction) if a.optimizer == "lm" else None
-    if lm_stats is not None and (a.lm_starts > 1 or a.lm_explore_one):
-        lm_stats["multistart"] = multistart_record(run, a, world)
-    memory = None
-    if gpu:
-        # HBM footprint of this rank (every buffer is a torch allocation): the
-        # 288 GB-per-GPU sizing of the 64M-path basket config
-        n_dates_m = run.paths.n_coarse - 1
-        pb = sum(int(t.numel()) * t.element_size() for t in (run.paths.S, run.paths.vol, run.paths.nfrac,
-                                                              run.paths.lam, run.paths.S_final) if t is not None)
-        mx = int(torch.cuda.max_memory_allocated(run.device))
-        memory = {"max_allocated_bytes": mx, "path_buffer_bytes": pb,
-                  "bytes_per_path": mx / run.n_local, "bytes_per_path_date": mx / (run.n_local * max(n_dates_m, 1)),
-                  "device_total_bytes": int(torch.cuda.get_device_properties(run.device).total_memory)}
+    lm = a.optimizer == "lm"
     n_total = run.n_total
     n_dates = run.paths.n_coarse - 1
-    lm = a.optimizer == "lm"
-    # full passes over the paths per run: Adam epochs, or LM evaluations (start point + trials)
-    passes = (a.lm_passes_first + 1 + (n_dates - 1) * (a.lm_passes_rest + 1)) if lm else \
-        (a.epochs_first + (n_dates - 1) * a.epochs_rest)
-    if lm and lm_stats and a.lm_stop_tol > 0:  # adaptive budget: the evaluations actually run
-        passes = sum(p + 1 for p in lm_stats["passes_per_date"])
-    if lm and lm_stats and lm_stats.get("multistart"):  # + the exploration, in full-pass equivalents
-        passes += lm_stats["multistart"]["full_pass_equivalents"]
-    path_samples = float(n_total) * passes / (ms / 1000.0)
     value = float(n_total) / (ms / 1000.0)
     out = {
         "metric": METRIC,
@@ -554,23 +590,25 @@ def main(argv=None):
                    "lm_dp_transport": (("gloo" if a.cpu else run.di.lm_dp_mode) if world > 1 and lm else None),
                    "dp_probe": probe, "dist_world": D.dist_world(),
                    "launch": "torchrun" if "TORCHELASTIC_RUN_ID" in os.environ or world > 1 else "single"},
+        # what the last timed step computed (HedgeRun.collect())
         "quality": {"terminal_pnl_std": res.terminal_pnl["std"], "terminal_pnl_mean": res.terminal_pnl["mean"],
                     "terminal_pnl_kind": res.terminal_pnl.get("kind"),
                     "terminal_residual_std": res.terminal_residual["std"],
                     "terminal_residual_mean": res.terminal_residual["mean"],
                     "V0": res.v0, "phi0": res.phi, "psi0": res.psi,
-                    "anchor": anchor(cfg), "hedge_anchor": delta_anchor(run, cfg),
                     "mc_discounted_payoff": res.summary["E_payoff"] * run.scale * math.exp(-cfg.r * cfg.T),
                     "reference_terminal_residual_std_52step": 1.7504, "reference_V0": 11.352},
-        "lm": lm_stats,
-        "lm_exchange": lm_exchange_record(run, a, world) if (lm and not a.cpu) else None,
-        "memory": memory,
-        "path_samples_per_s": path_samples, "full_passes_per_run": passes,
         # nodes of the replayed hipGraph (kernels + copies): the same at every
         # world size when the data-parallel exchange adds no launch
         "graph_nodes": int(run.graph.num_nodes) if (use_graph and run.graph is not None) else None,
-        "path_samples_vs_keras": path_samples / BASELINE_SAMPLES_PER_S,
+        "full": bool(a.full),
     }
+    if a.full:
+        extra = full_report(a, cfg, run, res, world, ms, gpu)
+        out["quality"].update(extra.pop("quality"))
+        out.update(extra)
+    if a.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(a.dump_outputs, run, res)
     if rank == 0:
         line = json.dumps(out)
         print(line, flush=True)
@@ -580,6 +618,47 @@ def main(argv=None):
     run.close()
     D.shutdown()
     return 0
+
+
+def full_report(a, cfg, run, res, world: int, ms: float, gpu: bool) -> dict:
+    """--full: the records that take work of their own after the timed steps
+    (collective on every rank): the closed-form price and the analytic hedge on
+    the same paths, LM fit statistics, data-parallel exchange volume, memory
+    footprint and the round-1 path-samples/s unit.  Returns the result line's
+    extra fields; ``quality`` is the line's own with the anchors added."""
+    lm_stats = lm_fit_stats(res.induction) if a.optimizer == "lm" else None
+    if lm_stats is not None and (a.lm_starts > 1 or a.lm_explore_one):
+        lm_stats["multistart"] = multistart_record(run, a, world)
+    memory = None
+    if gpu:
+        # HBM footprint of this rank (every buffer is a torch allocation): the
+        # 288 GB-per-GPU sizing of the 64M-path basket config (DESIGN.md)
+        n_dates_m = run.paths.n_coarse - 1
+        pb = sum(int(t.numel()) * t.element_size() for t in (run.paths.S, run.paths.vol, run.paths.nfrac,
+                                                              run.paths.lam, run.paths.S_final) if t is not None)
+        mx = int(torch.cuda.max_memory_allocated(run.device))
+        memory = {"max_allocated_bytes": mx, "path_buffer_bytes": pb,
+                  "bytes_per_path": mx / run.n_local, "bytes_per_path_date": mx / (run.n_local * max(n_dates_m, 1)),
+                  "device_total_bytes": int(torch.cuda.get_device_properties(run.device).total_memory)}
+    n_total = run.n_total
+    n_dates = run.paths.n_coarse - 1
+    lm = a.optimizer == "lm"
+    # full passes over the paths per run: Adam epochs, or LM evaluations (start point + trials)
+    passes = (a.lm_passes_first + 1 + (n_dates - 1) * (a.lm_passes_rest + 1)) if lm else \
+        (a.epochs_first + (n_dates - 1) * a.epochs_rest)
+    if lm and lm_stats and a.lm_stop_tol > 0:  # adaptive budget: the evaluations actually run
+        passes = sum(p + 1 for p in lm_stats["passes_per_date"])
+    if lm and lm_stats and lm_stats.get("multistart"):  # + the exploration, in full-pass equivalents
+        passes += lm_stats["multistart"]["full_pass_equivalents"]
+    path_samples = float(n_total) * passes / (ms / 1000.0)
+    return {
+        "quality": {"anchor": anchor(cfg), "hedge_anchor": delta_anchor(run, cfg)},
+        "lm": lm_stats,
+        "lm_exchange": lm_exchange_record(run, a, world) if (lm and not a.cpu) else None,
+        "memory": memory,
+        "path_samples_per_s": path_samples, "full_passes_per_run": passes,
+        "path_samples_vs_keras": path_samples / BASELINE_SAMPLES_PER_S,
+    }
 
 
 if __name__ == "__main__":

@@ -53,13 +53,65 @@ def _bench(args, env=None, nproc=1, bare=False):
 
 
 def test_bench_cpu_preset_contract():
-    r = _bench(["--preset", "euro1_cpu", "--steps", "1", "--warmup", "0", "--epochs-first", "20"])
-    assert KEYS <= set(r)
+    r = _bench(["--preset", "euro1_cpu", "--steps", "1", "--warmup", "0", "--epochs-first", "20", "--full"])
+    assert KEYS <= set(r) and r["full"] is True
     assert r["n_gpus"] == 1 and r["steps"] == 1 and r["higher_is_better"] is True and r["scaling"] == "weak"
     assert r["config"]["preset"] == "euro1_cpu" and r["config"]["parallelism"] == "dp1"
     assert r["value"] > 0 and r["vs_baseline"] == pytest.approx(r["value"] / (4096.0 / ((500 + 29 * 904 / 51) * 0.048)))
     assert r["path_samples_per_s"] == pytest.approx(r["value"] * r["full_passes_per_run"])
     assert r["quality"]["anchor"]["analytic"] == "black_scholes"
+
+
+FULL_ONLY = {"lm", "lm_exchange", "memory", "path_samples_per_s", "full_passes_per_run", "path_samples_vs_keras"}
+
+
+def _check_dump(d, r, dates, paths):
+    """The --dump-outputs files of result line ``r``: names, dtypes, shapes, and
+    the summary / date sums agree with the line's own quality record."""
+    names = {"values", "values_index", "weights", "date_stats", "pnl_stats", "summary"}
+    assert {f[:-4] for f in os.listdir(d)} == names and set(r["dumped_outputs"]) == names
+    a = {k: np.load(os.path.join(d, k + ".npy")) for k in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["values"].shape == (dates + 1, paths) and a["values"].dtype == np.float32
+    assert np.array_equal(a["values_index"], np.arange(paths))  # everything fits: no sampling
+    assert a["weights"].shape[:2] == (dates, 2) and a["date_stats"].shape[0] == dates
+    assert all(np.isfinite(v).all() for v in a.values())
+    q = r["quality"]
+    assert a["summary"].tolist() == [q["V0"], q["phi0"], q["psi0"], q["terminal_pnl_std"], q["terminal_pnl_mean"],
+                                     q["terminal_residual_std"], q["terminal_residual_mean"],
+                                     q["mc_discounted_payoff"]]
+    # V_0 is one number per run: the date-0 value of every path is the mean the line reports (fp32 storage)
+    assert float(a["values"][0].astype(np.float64).mean()) * 100.0 == pytest.approx(q["V0"], rel=1e-5)
+    return a
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline fields and what its last step computed,
+    none of the --full records; --dump-outputs writes that step's arrays, the
+    same in a second run with the same arguments (identical inputs)."""
+    args = ["--preset", "euro1_cpu", "--steps", "2", "--warmup", "0", "--epochs-first", "8", "--paths-log2", "10",
+            "--batch-log2", "8"]
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    r = _bench(args + ["--dump-outputs", d1])
+    assert KEYS <= set(r) and r["full"] is False and r["steps"] == 2 and r["ms_per_step"] > 0
+    assert not (FULL_ONLY & set(r)) and not ({"anchor", "hedge_anchor"} & set(r["quality"]))
+    a = _check_dump(d1, r, 1, 1 << 10)
+    r2 = _bench(args + ["--dump-outputs", d2])
+    for k, v in a.items():
+        assert np.array_equal(v, np.load(os.path.join(d2, k + ".npy"))), k
+    assert r2["quality"] == r["quality"]
+
+
+@pytest.mark.gpu
+def test_bench_gpu_dump_outputs(tmp_path):
+    """--dump-outputs on the GPU path (graph replay, LM fits, 6 dates, 2^16
+    paths): the arrays of the last replay, consistent with the result line."""
+    d = str(tmp_path / "o")
+    r = _bench(["--steps", "2", "--warmup", "1", "--paths-log2", "16", "--dates", "6", "--dump-outputs", d])
+    assert r["config"]["backend"] == "hip" and r["config"]["graph"] is True and r["full"] is False
+    assert not (FULL_ONLY & set(r))
+    _check_dump(d, r, 6, 1 << 16)
 
 
 @pytest.mark.parametrize("nproc", [4, 8])

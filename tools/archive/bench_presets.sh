@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for p in ${PRESETS:-euro30 heston30 euro252 basket5}; do
   echo "=== preset $p"
-  timeout -k 10 ${PRESET_TIMEOUT:-300} python bench.py --preset $p --steps ${STEPS:-3} --warmup 1 \
+  timeout -k 10 ${PRESET_TIMEOUT:-300} python bench.py --full --preset $p --steps ${STEPS:-3} --warmup 1 \
       --json-out gpurun_out/preset_$p.json > gpurun_out/preset_$p.log 2>&1
   rc=$?
   tail -n 3 gpurun_out/preset_$p.log

@@ -29,7 +29,7 @@ def main():
             buf = io.StringIO()
             t0 = time.perf_counter()
             with contextlib.redirect_stdout(buf):
-                bench.main(rest + ["--seed", str(s)])
+                bench.main(rest + ["--full", "--seed", str(s)])
             line = [l for l in buf.getvalue().splitlines() if l.startswith("{")][-1]
             r = json.loads(line)
             q = r["quality"]

@@ -470,6 +470,9 @@ class HedgeRun:
                 if getattr(self, "_wq_resume", None) is not None:
                     set_weights(self.spec, ind.w_q, self._wq_resume)
             ind.opt_q.copy_(ind.opt_init)
+        # pinball LM fits: values[date] on the Gram subsample (not saved) from
+        # the restored networks - the first resumed fit's gram_target
+        ind.restore_gram_values(date)
         # the first resumed date is NOT the reference's "first" date (no LR schedule)
         orig = ind._fcfg
         ind._fcfg = lambda first, loss, t=None: orig(False, loss, t)

@@ -219,7 +219,8 @@ class BackwardInduction:
                      and gram_paths is not None and gram_terminal is not None)
         if q_lm_side:
             ns = gram_terminal.numel()
-            self.gvalues = torch.empty(nc, ns, dtype=torch.float32, device=dev)
+            # (NaN-filled: a row read as a fit target before it is written fails loudly)
+            self.gvalues = torch.full((nc, ns), float("nan"), dtype=torch.float32, device=dev)
             self.gvalues[nc - 1].copy_(gram_terminal)
             self.g_terminal = gram_terminal
             self.ggbuf = torch.empty(ns, dtype=torch.float32, device=dev)
@@ -321,6 +322,31 @@ class BackwardInduction:
                         target=self.gvalues[t + 1], prices_now=gp.prices(t), bond_now=float(gp.bond[t]),
                         fmu=mu, fisd=isd)
 
+    def eval_gram_values(self, t: int, with_target: bool = True):
+        """``gvalues[t]``: the two-network blend of date t (the current MSE and
+        Q99 weights) on the Gram subsample - V_t there, the next date's
+        pinball-fit targets.  ``with_target=False`` leaves V_{t+1} out (resume:
+        only ``gvalues[t]`` itself is restored, and V_t does not depend on it)."""
+        c, be = self.cfg, self.backend
+        gd = self.gram_date_data(t)
+        if not with_target:
+            gd.target = None
+        ns = self.ggbuf.numel()
+        be.eval(self.w_mse, gd, self.gstats[0], v_out=self.ggbuf, n_local=ns)
+        be.eval(self.w_mse, gd, self.gstats[1], wts_b=self.w_q, g_base=self.ggbuf,
+                blend_c=c.cost_of_capital, hold_c=self.hold_c, v_out=self.gvalues[t], n_local=ns)
+
+    def restore_gram_values(self, date: int):
+        """Resume at ``date``: rebuild ``gvalues[date]``, the Gram-subsample
+        targets of the first resumed pinball LM fit, from the restored weights
+        (the terminal row is the subsample's payoff)."""
+        if self.gvalues is None:
+            return
+        if date >= self.paths.n_coarse - 1:
+            self.gvalues[date].copy_(self.g_terminal)
+        else:
+            self.eval_gram_values(date, with_target=False)
+
     def enqueue(self, start: int | None = None):
         """Enqueue dates ``start, start-1, ..., 0`` (default: all, from n-2).
         Resume restarts at ``start = i-1`` after loading the
@@ -377,14 +403,8 @@ class BackwardInduction:
                 be.eval(self.w_mse, data, s_q, wts_b=self.w_q, g_base=self.gbuf, blend_c=c.cost_of_capital,
                         hold_c=self.hold_c, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
                         snap_a=self.snap[t, 0], snap_b=self.snap[t, 1])
-                if self.gvalues is not None and t > 0:
-                    # the same blend on the Gram subsample: V_t there, the next
-                    # date's pinball-fit targets
-                    gd = self.gram_date_data(t)
-                    ns = self.ggbuf.numel()
-                    be.eval(self.w_mse, gd, self.gstats[0], v_out=self.ggbuf, n_local=ns)
-                    be.eval(self.w_mse, gd, self.gstats[1], wts_b=self.w_q, g_base=self.ggbuf,
-                            blend_c=c.cost_of_capital, hold_c=self.hold_c, v_out=self.gvalues[t], n_local=ns)
+                if self.gvalues is not None:
+                    self.eval_gram_values(t)
             else:
                 be.eval(self.w_mse, data, s_q, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
                         snap_a=self.snap[t, 0])

@@ -413,6 +413,18 @@ def _normalise(X: torch.Tensor, data: DateData) -> torch.Tensor:
     return (X - mu) * isd
 
 
+def _check_eval_data(spec: NetSpec, data: DateData):
+    """Reject eval inputs the epilogue has no defined result for (both backends)."""
+    na = spec.nhold - 1
+    if len(data.prices_now) != na:
+        raise ValueError(f"eval needs {na} prices_now tensor(s), got {len(data.prices_now)}")
+    if len(data.prices_next) not in (0, na):
+        raise ValueError(f"eval needs {na} prices_next tensor(s) or none, got {len(data.prices_next)}")
+    if not data.prices_next and data.target is not None:
+        raise ValueError("eval with a target needs prices_next: the residual V_{t+1} - h . p_{t+1} is undefined "
+                         "without them (pass target=None for the values / holdings alone)")
+
+
 def fit_seed(seed: int, date: int, net: int) -> int:
     return (int(seed) * 1000003 + int(date) * 7919 + int(net) * 104729) & 0xFFFFFFFF
 
@@ -1152,6 +1164,7 @@ class HipBackend:
              n_local: int | None = None):
         """k_hedge_eval over ``data`` (``n_local``: its path count when it is
         not this backend's shard, e.g. the Gram subsample)."""
+        _check_eval_data(self.spec, data)
         n = self.native
         d = n.EvalDesc()
         d.snap_a = snap_a.data_ptr() if snap_a is not None else None
@@ -1678,6 +1691,7 @@ class TorchBackend:
              n_local: int | None = None):
         spec, dt = self.spec, torch.float32
         P = spec.nparams
+        _check_eval_data(spec, data)
         if snap_a is not None:
             snap_a.copy_(wts)
         if snap_b is not None:

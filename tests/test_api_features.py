@@ -312,6 +312,114 @@ def test_resume_from_saved_date(tmp_path):
     assert res.v0 == pytest.approx(full.v0, rel=0.05)
 
 
+def _gram_blend_f64(ind, t, w_a, w_b):
+    """fp64 V_t of the two-network blend g + c (V_B - g) on the Gram subsample,
+    from flat (standardised-input) weights of date t."""
+    from rphedge.models.hedge_mlp import torch_forward
+
+    gp, spec = ind.gram_paths, ind.spec
+    X = torch.stack([f.detach().cpu().double() for f in gp.features(t)], dim=1)
+    if ind.norms:
+        mu, isd = ind.norms[t]
+        X = (X - torch.tensor(mu, dtype=torch.float64)) * torch.tensor(isd, dtype=torch.float64)
+    pr = [p.detach().cpu().double() for p in gp.prices(t)]
+    pr = torch.stack(pr + [torch.full_like(pr[0], float(gp.bond[t]))], dim=1)
+    g = (torch_forward(spec, torch.from_numpy(w_a).double(), X) * pr).sum(dim=1)
+    vb = (torch_forward(spec, torch.from_numpy(w_b).double(), X) * pr).sum(dim=1)
+    return (g + float(ind.cfg.cost_of_capital) * (vb - g)).numpy()
+
+
+def check_lm_resume(out_dir, device, n_paths_log2, date=5):
+    """Resume of a run whose pinball fits are IRLS LM fits on the Gram
+    subsample: ``gvalues[date]`` (the first resumed fit's targets, not saved)
+    is rebuilt from the restored networks.  Shared with the GPU twin
+    (test_gpu_resume_lm.py).  Returns the measured figures."""
+    from rphedge import experiments
+    from rphedge.api import HedgeRun
+    from rphedge.config import parse_params
+    from rphedge.engine import current_weights
+    from rphedge.models.hedge_mlp import fold_input_norm, unfold_input_norm
+    from rphedge.utils.model_io import save_run
+
+    p = experiments.mts_lm_parameters(n_paths=n_paths_log2, dt=0.1, rebalancing=1.0, device=device, verbose=False,
+                                      lm_starts=4, lm_explore_passes=10, lm_explore_log2=9, lm_passes_first=20,
+                                      lm_q_passes_first=30, lm_q_passes_rest=5)
+    run = HedgeRun(parse_params(p))
+    full = run.run()
+    ind = run.induction
+    assert ind.gvalues is not None and ind.q_lm
+    save_run(str(out_dir), run, full)
+    run2 = HedgeRun(parse_params(p))
+    res = run2.resume(str(out_dir), date)
+    ind2 = run2.induction
+    g_full = ind.gvalues.detach().cpu().numpy().astype(np.float64)
+    g_res = ind2.gvalues.detach().cpu().numpy().astype(np.float64)
+    # every row the resumed scan reads or writes is defined
+    assert not np.isnan(g_res[:date + 1]).any(), np.isnan(g_res).any(axis=1)
+
+    # tolerance of gvalues[date]: the saved weights went through the fp32
+    # fold (raw-input, saved) / unfold (this run's standardisation) round trip;
+    # its effect on V is measured in fp64 on the weights alone, and each side's
+    # fp32 evaluation adds the per-path bound of the eval epilogue
+    # (32 * 2^-24 * max|V|, tests/test_gpu_eval.py)
+    mu, isd = ind.norms[date]
+    snap = ind.snap.detach().cpu()
+    wa, wb = (current_weights(ind.spec, snap[date, k]) for k in (0, 1))
+    rt = [unfold_input_norm(ind.spec, fold_input_norm(ind.spec, w, mu, isd), mu, isd) for w in (wa, wb)]
+    v_ref = _gram_blend_f64(ind, date, wa, wb)
+    d_rt = float(np.abs(_gram_blend_f64(ind, date, rt[0], rt[1]) - v_ref).max())
+    vmax = float(np.abs(v_ref).max())
+    tol = d_rt + 2 * 32 * 2.0 ** -24 * vmax
+    err = float(np.abs(g_res[date] - g_full[date]).max())
+    print(f"lm resume [{device}]: gvalues[{date}] max|resumed - full| = {err:.3e}, weight round trip {d_rt:.3e}, "
+          f"tolerance {tol:.3e} (max|V| {vmax:.3f})")
+    assert err <= tol, (err, tol, d_rt)
+
+    assert [d.index for d in res.induction.dates] == list(range(date - 1, -1, -1))
+    for d in res.induction.dates:
+        h = d.fit_q99["history"]
+        assert len(h) > 1 and math.isfinite(d.fit_q99["best_loss"]) and d.fit_q99["best_loss"] <= h[0], (d.index, h)
+    assert math.isfinite(res.phi) and math.isfinite(res.v0)
+    assert res.v0 == pytest.approx(full.v0, rel=0.05)
+    return err, d_rt, tol
+
+
+def test_resume_lm_pinball_restores_gram_values(tmp_path):
+    """Resume with ``q99_optimizer="lm"`` (the mts_lm_parameters configuration
+    of test_pension_lm_preset_cpu): the resumed run rebuilds ``gvalues[5]``.
+    It used to stay uninitialised memory and the first resumed pinball fit
+    read it as its Gram targets (resumed values 2 % off the full run).
+
+    Measured on the torch backend (2^10 paths): max|resumed - full| of
+    gvalues[5] 7.2e-7 at max|V| 4.35, weight round trip 4.1e-7 in fp64,
+    tolerance 1.7e-5."""
+    check_lm_resume(tmp_path, "cpu", 10)
+
+
+def test_eval_rejects_target_without_next_prices():
+    """``prices_next=[]`` with a target has no defined residual (the HIP
+    epilogue would report 0, the torch oracle ``target - 0``): both backends
+    reject it on the host; without a target it is the values-only form."""
+    from rphedge.engine import DateData, TorchBackend, TrainConfig
+    from rphedge.models.hedge_mlp import NetSpec, init_weights
+    from rphedge.ops import layout as L
+
+    spec = NetSpec(nin=1, hidden=8, nout=2, head=0)
+    n = 16
+    x = torch.linspace(0.8, 1.2, n)
+    be = TorchBackend(spec, n, TrainConfig(batch_size=n))
+    w, st = be.new_weights(init_weights(spec, [0.5, 0.1])), be.new_stats()
+    with pytest.raises(ValueError, match="prices_next"):
+        be.eval(w, DateData(feats=[x], prices_next=[], bond_next=1.0, target=torch.relu(x - 1), prices_now=[x]), st)
+    with pytest.raises(ValueError, match="prices_now"):
+        be.eval(w, DateData(feats=[x], prices_next=[x], bond_next=1.0, target=None, prices_now=[]), st)
+    v, r = torch.empty(n), torch.empty(n)
+    be.eval(w, DateData(feats=[x], prices_next=[], bond_next=1.0, target=None, prices_now=[x]), st, v_out=v,
+            resid_out=r)
+    assert torch.isfinite(v).all() and float(r.abs().max()) == 0.0
+    assert float(st[0, L.ES_PRED1]) == 0.0 and float(st[0, L.ES_COUNT]) == n
+
+
 def test_nan_gradient_guard_cpu():
     """Fault injection: a NaN target poisons the gradient -> the update is
     skipped and counted, weights stay finite."""

@@ -161,15 +161,46 @@ def test_mortality_statistics(dev):
     assert 110 < nT.std() < 160
 
 
-def _fit_pair(dev, spec, n, batch, epochs, loss, chunk_log2=0, lr=1e-2, norm=None, **tkw):
-    from rphedge.engine import DateData, FitConfig, HipBackend, TorchBackend, TrainConfig, current_weights
-    from rphedge.models.hedge_mlp import init_weights
-    from rphedge.ops import layout as L
-
+def _fit_inputs(spec, n):
     g = torch.Generator().manual_seed(0)
     feats = [torch.rand(n, generator=g) * 0.5 + 0.75 for _ in range(spec.nin)]
     prices = [f.clone() * (1 + 0.05 * torch.randn(n, generator=g)) for f in feats[: spec.nhold - 1]]
     target = torch.relu(prices[0] - 1.0) if spec.nhold > 1 else torch.rand(n)
+    return feats, prices, target
+
+
+def _check_fit_stats(spec, sc, sg, vc, rc, rtol, atol):
+    """The eval statistics (reduce_stats of the slab) of a _fit_pair, HIP vs
+    torch, at the elementwise tolerance ``atol + rtol |ref|`` the test grants
+    the fitted values and residuals (the holdings take the same): every sum is
+    allowed the sum of its paths' tolerances."""
+    from rphedge.ops import layout as L
+
+    n = vc.size
+    assert sg[L.ES_COUNT] == sc[L.ES_COUNT] == n
+    target = _fit_inputs(spec, n)[2].double().numpy()
+    vc, rc = vc.astype(np.float64), rc.astype(np.float64)
+    dv, dr = atol + rtol * np.abs(vc), atol + rtol * np.abs(rc)
+    tol = {L.ES_V: dv.sum(), L.ES_V2: (2 * np.abs(vc) * dv + dv * dv).sum(),
+           L.ES_RES: dr.sum(), L.ES_RES2: (2 * np.abs(rc) * dr + dr * dr).sum(), L.ES_ABSRES: dr.sum(),
+           L.ES_APE: (dr / np.maximum(np.abs(target), 1e-7)).sum(), L.ES_PRED1: dr.sum(),
+           L.ES_RESMIN: dr.max(), L.ES_RESMAX: dr.max()}
+    for k in range(spec.nhold):
+        h2 = float(sc[L.ES_HOLD2 + k])
+        habs = math.sqrt(n * h2)  # >= sum|h| (Cauchy-Schwarz)
+        tol[L.ES_HOLD + k] = n * atol + rtol * habs
+        tol[L.ES_HOLD2 + k] = 2 * atol * habs + 2 * rtol * h2 + 2 * n * atol * atol + 2 * rtol * rtol * h2
+    for idx, t in tol.items():
+        assert abs(sg[idx] - sc[idx]) <= t, (idx, sg[idx], sc[idx], t)
+
+
+def _fit_pair(dev, spec, n, batch, epochs, loss, chunk_log2=0, lr=1e-2, norm=None, **tkw):
+    from rphedge.engine import (DateData, FitConfig, HipBackend, TorchBackend, TrainConfig, current_weights,
+                                reduce_stats)
+    from rphedge.models.hedge_mlp import init_weights
+    from rphedge.ops import layout as L
+
+    feats, prices, target = _fit_inputs(spec, n)
     w0 = init_weights(spec, ([0.5] + [-0.4] * (spec.nout - 1)) if spec.head == 0 else [0.1])
     tc = TrainConfig(batch_size=batch, chunk_log2=chunk_log2, lr=lr, **tkw)
     fc = FitConfig(epochs=epochs, patience=1000, loss=loss, early_stopping=False)
@@ -189,7 +220,7 @@ def _fit_pair(dev, spec, n, batch, epochs, loss, chunk_log2=0, lr=1e-2, norm=Non
         if d.type == "cuda":
             torch.cuda.synchronize()
         out.append((current_weights(spec, w), o.cpu().numpy(), f.cpu().numpy(), vo.cpu().numpy(), ro.cpu().numpy(),
-                    st.sum(0).cpu().numpy()))
+                    reduce_stats(st)))
     return out
 
 
@@ -218,6 +249,7 @@ def test_train_step_matches_torch(dev, shape, mode):
     np.testing.assert_allclose(fg[L.F_HIST:L.F_HIST + 2], fc[L.F_HIST:L.F_HIST + 2], rtol=1e-3)
     np.testing.assert_allclose(vg, vc, rtol=1e-3, atol=1e-4)
     np.testing.assert_allclose(rg, rc, rtol=1e-3, atol=1e-4)
+    _check_fit_stats(spec, sc, sg, vc, rc, rtol=1e-3, atol=1e-4)
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5])
@@ -237,6 +269,7 @@ def test_narrow_lag_variants_match_torch(dev, shape, variant):
     np.testing.assert_allclose(wg, wc, rtol=2e-3, atol=2e-4)
     np.testing.assert_allclose(fg[L.F_HIST:L.F_HIST + 2], fc[L.F_HIST:L.F_HIST + 2], rtol=1e-3)
     np.testing.assert_allclose(vg, vc, rtol=1e-3, atol=1e-4)
+    _check_fit_stats(spec, sc, sg, vc, rc, rtol=1e-3, atol=1e-4)
 
 
 def _norm(nin):
@@ -259,6 +292,7 @@ def test_feature_norm_matches_torch(dev, shape, mode):
     np.testing.assert_allclose(fg[L.F_HIST:L.F_HIST + 2], fc[L.F_HIST:L.F_HIST + 2], rtol=1e-3)
     np.testing.assert_allclose(vg, vc, rtol=1e-3, atol=2e-4)
     np.testing.assert_allclose(rg, rc, rtol=1e-3, atol=2e-4)
+    _check_fit_stats(spec, sc, sg, vc, rc, rtol=1e-3, atol=2e-4)
 
 
 @pytest.mark.parametrize("det,split", [(False, False), (True, False), (False, True)])
@@ -393,6 +427,7 @@ def test_deterministic_mode_is_bitwise_reproducible(dev):
     a = _fit_pair(dev, spec, 1 << 16, 1 << 15, 2, L.LOSS_MSE, chunk_log2=6, deterministic=True)[1]
     b = _fit_pair(dev, spec, 1 << 16, 1 << 15, 2, L.LOSS_MSE, chunk_log2=6, deterministic=True)[1]
     assert np.array_equal(a[0], b[0])
+    assert np.array_equal(a[5], b[5])  # (the eval statistics: no atomics, a fixed reduction order)
 
 
 def test_rccl_comm_split_update_and_graph_capture(dev):

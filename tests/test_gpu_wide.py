@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_kernels import _fit_pair, dev  # noqa: F401  (fixture)
+from test_gpu_kernels import _check_fit_stats, _fit_pair, dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +34,7 @@ def test_wide_fp32_mfma_matches_torch(dev, shape, mode):  # noqa: F811
     np.testing.assert_allclose(fg[L.F_HIST:L.F_HIST + 2], fc[L.F_HIST:L.F_HIST + 2], rtol=1e-3)
     np.testing.assert_allclose(wg, wc, rtol=3e-3, atol=3e-4)
     np.testing.assert_allclose(vg, vc, rtol=2e-3, atol=2e-4)
+    _check_fit_stats(spec, sc, sg, vc, rc, rtol=2e-3, atol=2e-4)
 
 
 @pytest.mark.parametrize("mode", ["auto", "persistent"])
@@ -52,6 +53,9 @@ def test_wide_bf16_mfma_matches_torch(dev, shape, mode):  # noqa: F811
     scale = np.abs(vc).mean()
     assert np.abs(vg - vc).mean() < 2e-2 * scale
     assert np.corrcoef(vg, vc)[0, 1] > 0.999
+    # the statistics slab: the mean-error bound above, summed
+    assert sg[L.ES_COUNT] == sc[L.ES_COUNT] == vc.size
+    assert abs(sg[L.ES_V] - sc[L.ES_V]) < 2e-2 * np.abs(vc).sum()
 
 
 @pytest.mark.parametrize("det,split", [(False, False), (True, False), (False, True)])
@@ -77,6 +81,7 @@ def test_wide_deterministic_bitwise(dev):  # noqa: F811
     b = _fit_pair(dev, spec, 1 << 16, 1 << 15, 2, L.LOSS_MSE, chunk_log2=6, deterministic=True)[1]
     assert np.array_equal(a[0], b[0])
     assert np.array_equal(a[3], b[3])
+    assert np.array_equal(a[5], b[5])
 
 
 @pytest.mark.parametrize("feature_norm", ["none", "date"])

@@ -1,10 +1,13 @@
 // rphedge — Monte-Carlo path generation for gfx950:
 //   K1  scrambled Sobol (index-addressable, bit-exact with scipy.stats.qmc.Sobol)
 //   K2  inverse normal CDF fused into K1 (fp32 Giles / fp64 Acklam+Halley)
-//   K3  GBM scans (arithmetic Euler RP:64-65, log-Euler EO:161-165), basket
+//   K3  GBM scans (arithmetic Euler RP:64-65, log-Euler EO:161-165), basket;
+//       optional running statistic of the fine GBM path (mean / geometric
+//       mean / max / min: Asian and lookback options)
 //   K4  SV scans (reference CIR-on-sigma RP:282-289; full-truncation Heston)
 //   K5+K6 mortality intensity Euler + binomial survivors (RP:71-84)
-//   K7  payoffs (guarantee RP:88/:184, call/put EO:328-329, basket call)
+//   K7  payoffs (guarantee RP:88/:184, call/put EO:328-329, basket call,
+//       floating strike)
 //
 // One thread per path; the time recursion lives in registers; Sobol normals
 // are regenerated on the fly (W is never stored); only the coarse rebalancing
@@ -59,7 +62,11 @@ RPH_INLINE long long sim_gidx(const SimDesc& d, int p) {
 // ---------------------------------------------------------------------------
 // Single-asset / SV / Heston / mortality scans.
 // ---------------------------------------------------------------------------
-template <typename Real, bool ALIGNED, int MODEL>
+// STAT (GBM models only; PathStat in rph_types.h): a running statistic of the
+// FINE-grid path, monitored at the fine points j = 1..t (max / min also at
+// j = 0), kept in a register beside the state and stored to out2 / final2_out
+// exactly like the price.  STAT = 0 is the plain scan.
+template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
 __global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (!ALIGNED && p >= d.n_local) return;
@@ -76,18 +83,40 @@ __global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
     const Real drift = (MODEL == SIM_GBM_LOG) ? (mu - (Real)0.5 * sig * sig) * dt : mu * dt;
     const Real vol = sig * sdt;
     d.out[p] = (float)d.s0[0] * inv0;
+    // running sum of S (mean) / of log S (geomean), or running extreme from S_0
+    Real acc = (STAT == STAT_MEAN || STAT == STAT_GEOMEAN) ? (Real)0 : (Real)d.s0[0];
+    Real stat = (Real)d.s0[0];  // the statistic at the current fine point (S_0 at j = 0)
+    Real sf = (Real)d.s0[0];    // S at the current fine point (STAT: mean / max / min)
+    if (STAT != STAT_NONE) d.out2[p] = (float)d.s0[0] * inv0;
     for (int t = 1; t < d.n_fine; ++t) {
       const Real z = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
       if (MODEL == SIM_GBM_LOG) y += drift + vol * z;
       else y = y + y * (drift + vol * z);
+      if (STAT == STAT_GEOMEAN) {
+        acc += y;  // (log scheme only: the sum of log S, no exp per step)
+      } else if (STAT != STAT_NONE) {
+        sf = (MODEL == SIM_GBM_LOG) ? exp(y) : y;
+        if (STAT == STAT_MEAN) acc += sf;
+        else if (STAT == STAT_MAX) acc = sf > acc ? sf : acc;
+        else acc = sf < acc ? sf : acc;
+      }
+      if (t % d.reduction == 0 || (STAT != STAT_NONE && t == d.n_fine - 1)) {
+        if (STAT == STAT_MEAN) stat = acc / (Real)t;
+        else if (STAT == STAT_GEOMEAN) stat = exp(acc / (Real)t);
+        else if (STAT != STAT_NONE) stat = acc;
+      }
       if (t % d.reduction == 0) {
         const int c = t / d.reduction;
-        const Real s = (MODEL == SIM_GBM_LOG) ? exp(y) : y;
-        if (c < d.n_coarse) d.out[(size_t)c * n + p] = (float)s * inv0;
+        const Real s = (STAT != STAT_NONE && STAT != STAT_GEOMEAN) ? sf : ((MODEL == SIM_GBM_LOG) ? exp(y) : y);
+        if (c < d.n_coarse) {
+          d.out[(size_t)c * n + p] = (float)s * inv0;
+          if (STAT != STAT_NONE) d.out2[(size_t)c * n + p] = (float)stat * inv0;
+        }
       }
     }
-    const Real s = (MODEL == SIM_GBM_LOG) ? exp(y) : y;
+    const Real s = (STAT != STAT_NONE && STAT != STAT_GEOMEAN) ? sf : ((MODEL == SIM_GBM_LOG) ? exp(y) : y);
     if (d.final_out) d.final_out[p] = (float)s * inv0;
+    if (STAT != STAT_NONE && d.final2_out) d.final2_out[p] = (float)stat * inv0;
   } else if (MODEL == SIM_SV_REF || MODEL == SIM_HESTON) {
     // table 1 -> price shocks (W1, seed 1235), table 2 -> variance shocks (W_SV)
     Real ly = log((Real)d.s0[0]);
@@ -282,10 +311,13 @@ __global__ __launch_bounds__(256) void k_sim_basket(const SimDesc d) {
 //   0 guarantee: max(Y_T, K) * N_T/N      (RP:88, :184)
 //   1 call: max(S_T - K, 0)   2 put: max(K - S_T, 0)   (EO cell 8)
 //   3 basket call: max(sum_a w_a S_a,T - K, 0)
+//   4 floating-strike call: max(s - x, 0)   5 floating-strike put: max(x - s, 0)
+//     (x: a second per-path array, e.g. the path's running mean / extreme)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_payoff(int kind, int n, int na, const float* __restrict__ s,
                                                 const float* __restrict__ nfrac, float strike,
-                                                const float* __restrict__ wts, float* __restrict__ out) {
+                                                const float* __restrict__ wts, const float* __restrict__ x,
+                                                float* __restrict__ out) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   float v;
@@ -296,6 +328,10 @@ __global__ __launch_bounds__(256) void k_payoff(int kind, int n, int na, const f
     v = fmaxf(s[p] - strike, 0.f);
   } else if (kind == 2) {
     v = fmaxf(strike - s[p], 0.f);
+  } else if (kind == 4) {
+    v = fmaxf(s[p] - x[p], 0.f);
+  } else if (kind == 5) {
+    v = fmaxf(x[p] - s[p], 0.f);
   } else {
     float b = 0.f;
     for (int a = 0; a < na; ++a) b = fmaf(wts[a], s[(size_t)a * n + p], b);
@@ -350,9 +386,26 @@ extern "C" int rph_sobol_normal(void* out, int n, int d, const uint32_t* sv, con
   return (int)hipGetLastError();
 }
 
+// GBM scans with a running path statistic (SimDesc.path_stat, validated by rph_simulate)
+template <typename Real, bool AL, int MODEL>
+static int launch_scan_stat(const SimDesc* d, hipStream_t s) {
+  const dim3 grid(grid_for(d->n_local)), block(256);
+  switch (d->path_stat) {
+    case STAT_MEAN: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MEAN>), grid, block, 0, s, *d); break;
+    case STAT_GEOMEAN: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_LOG, STAT_GEOMEAN>), grid, block, 0, s, *d); break;
+    case STAT_MAX: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MAX>), grid, block, 0, s, *d); break;
+    case STAT_MIN: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MIN>), grid, block, 0, s, *d); break;
+    default: return -1;
+  }
+  return (int)hipGetLastError();
+}
+
 template <typename Real, bool AL>
 static int launch_scan(const SimDesc* d, hipStream_t s) {
   const dim3 grid(grid_for(d->n_local)), block(256);
+  if (d->path_stat != STAT_NONE)
+    return d->model == SIM_GBM_LOG ? launch_scan_stat<Real, AL, SIM_GBM_LOG>(d, s)
+                                   : launch_scan_stat<Real, AL, SIM_GBM_ARITH>(d, s);
   switch (d->model) {
     case SIM_GBM_ARITH: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_ARITH>), grid, block, 0, s, *d); break;
     case SIM_GBM_LOG: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_LOG>), grid, block, 0, s, *d); break;
@@ -382,6 +435,14 @@ static int launch_basket(const SimDesc* d, hipStream_t s) {
 extern "C" int rph_simulate(const SimDesc* d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (d->map_blk < 0 || (d->map_blk > 0 && d->map_stride < d->map_blk)) return rph_report("rph_simulate", "bad path-index map");
+  if (d->path_stat < STAT_NONE || d->path_stat > STAT_MIN) return rph_report("rph_simulate", "path_stat outside 0..4");
+  if (d->path_stat != STAT_NONE) {
+    if (d->model != SIM_GBM_ARITH && d->model != SIM_GBM_LOG)
+      return rph_report("rph_simulate", "path statistics need a GBM model");
+    if (!d->out2) return rph_report("rph_simulate", "path statistic without an out2 buffer");
+    if (d->path_stat == STAT_GEOMEAN && d->model != SIM_GBM_LOG)
+      return rph_report("rph_simulate", "geomean needs the log scheme (SIM_GBM_LOG)");
+  }
   // (aligned: every wave's 64 paths are one aligned range of global indices)
   const bool aligned = (d->n_local % 256 == 0) && (d->path_offset % 64 == 0) &&
                        (d->map_blk == 0 || (d->map_blk % 64 == 0 && d->map_stride % 64 == 0));
@@ -391,9 +452,10 @@ extern "C" int rph_simulate(const SimDesc* d, void* stream) {
 }
 
 extern "C" int rph_payoff(int kind, int n, int na, const float* s, const float* nfrac, float strike,
-                          const float* wts, float* out, void* stream) {
+                          const float* wts, const float* x, float* out, void* stream) {
+  if ((kind == 4 || kind == 5) && !x) return rph_report("rph_payoff", "floating-strike payoff without the x array");
   hipLaunchKernelGGL(k_payoff, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, kind, n, na, s, nfrac,
-                     strike, wts, out);
+                     strike, wts, x, out);
   return (int)hipGetLastError();
 }
 

@@ -410,7 +410,7 @@ struct SimDesc {
   // c sqrt(v dt*tscale) (tscale = 252 trading days per year)
   double sv_tscale;
   int scheme;                    // HESTON: 0 full-truncation Euler, 1 Andersen QE (martingale-corrected)
-  int pad0;
+  int path_stat;                 // PathStat: GBM running statistic of the fine path -> out2 / final2_out
   // path-index map (the LM Gram subsample simulated on every rank): local path
   // p is global path path_offset + (p / map_blk) * map_stride + p % map_blk;
   // map_blk = 0: contiguous (path_offset + p)
@@ -419,6 +419,16 @@ struct SimDesc {
 };
 
 enum HestonScheme : int { HESTON_EULER = 0, HESTON_QE = 1 };
+
+// Running statistic of the fine-grid GBM path at fine point j >= 1 (S_0 at
+// j = 0), monitored at the fine points 1..j (max / min: 0..j).
+enum PathStat : int {
+  STAT_NONE = 0,
+  STAT_MEAN = 1,      // (1/j) sum_{i=1..j} S_i
+  STAT_GEOMEAN = 2,   // exp((1/j) sum_{i=1..j} log S_i)   (log scheme only)
+  STAT_MAX = 3,       // max(S_0 .. S_j)
+  STAT_MIN = 4,       // min(S_0 .. S_j)
+};
 
 enum SimModel : int {
   SIM_GBM_ARITH = 0,   // Y_t = Y_{t-1}(1 + mu dt + sigma sqrt(dt) Z)   (RP:64-65)

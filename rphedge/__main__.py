@@ -1,7 +1,7 @@
 """Command line interface: ``python -m rphedge <command>``.
 
   run        --config cfg.json [--set key=value ...]   any params dict (pension, SV, European, basket)
-  european   [--paths N] [--parity] ...                  European Options notebook driver
+  european   [--paths N] [--parity] [--payoff NAME] ...   European Options notebook driver (NAME: asian_call ...)
   sts                                                    Single Time Step notebook driver
   sweep      [--sigmas .05,.1,...]                       volatility sweep (Multi Time Step)
   calibrate  --csv prices.csv | --synthetic               CIR calibration (Extra: Stochastic Volatility)
@@ -56,6 +56,8 @@ def main(argv=None) -> int:
     e.add_argument("--paths", type=int, default=3000)
     e.add_argument("--rebalancing", type=float, default=1 / 52)
     e.add_argument("--parity", action="store_true")
+    e.add_argument("--payoff", default=None,
+                   help="path-dependent option instead of the call: asian_call, geo_asian_call, lookback_call, ...")
     e.add_argument("--set", nargs="*", default=[])
     e.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
     sub.add_parser("sts").add_argument("--no-parity", action="store_true")
@@ -86,6 +88,8 @@ def main(argv=None) -> int:
         from .api import european_option
 
         extra = {k: _coerce(v) for k, v in (kv.split("=", 1) for kv in a.set)}
+        if a.payoff:
+            extra["payoff"] = a.payoff
         res = european_option(N_paths=a.paths, rebalancing_frequency=a.rebalancing, parity=a.parity, **extra)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))

@@ -84,6 +84,7 @@ class HedgeRun:
         self.n_total = 2 ** int(cfg.n_paths)
         self.offset, self.n_local = D.shard(self.n_total, dist_info.world, dist_info.rank)
         self.timer = PhaseTimer(enabled=True, device=self.device)
+        self.path_stat = None  # running path statistic of a path-dependent payoff (set by _kind)
         self.kind = self._kind()
         self.spec = self._spec()
         self.paths = None
@@ -98,6 +99,22 @@ class HedgeRun:
         c = self.cfg
         if c.payoff in ("call", "put"):
             return "european"
+        if c.payoff in P.PATH_PAYOFFS:
+            # path-dependent options (Asian / lookback): one GBM asset, the
+            # running statistic of the fine path as the second network input
+            self.path_stat = P.PATH_PAYOFFS[c.payoff][0]
+            bad = None
+            if c.model in ("heston", "basket", "sv_ref"):
+                bad = f"model {c.model!r} (path statistics run on the GBM models: gbm | gbm_log)"
+            elif c.parity.complement_head:
+                bad = "parity.complement_head (the psi = 1 - phi head takes one input)"
+            elif c.mortality:
+                bad = "mortality=True (a pension liability)"
+            elif self.path_stat == "geomean" and c.model == "gbm":
+                bad = "model 'gbm' (the arithmetic scheme; the geometric mean needs model='gbm_log')"
+            if bad:
+                raise ValueError(f"payoff {c.payoff!r} is not available with {bad}")
+            return "european"
         if c.payoff == "basket_call" or c.model == "basket":
             return "basket"
         return "pension"
@@ -107,6 +124,9 @@ class HedgeRun:
         alpha = c.train.leaky_alpha
         hid = int(c.train.hidden)
         if self.kind == "european":
+            if self.path_stat is not None:
+                # [S, statistic] -> (phi, psi); path_feature=False: S alone (the ablation)
+                return hm.NetSpec(nin=2 if c.path_feature else 1, hidden=hid, nout=2, head=L.HEAD_FREE, alpha=alpha)
             if c.model == "heston":
                 return hm.NetSpec(nin=2, hidden=hid, nout=2, head=L.HEAD_FREE, alpha=alpha)
             if c.parity.complement_head:
@@ -162,6 +182,8 @@ class HedgeRun:
     def _payoff(self, p: P.Paths, out=None) -> torch.Tensor:
         """Terminal value V_T of paths ``p`` (K7; ``out``: into that buffer)."""
         c = self.cfg
+        if self.path_stat is not None:
+            return P.payoff(c.payoff, p, c.K / c.Y, stream=self.stream, out=out)
         if self.kind == "european":
             return P.payoff(c.option_type.lower(), p, c.K / c.Y, stream=self.stream, out=out)
         if self.kind == "basket":
@@ -182,7 +204,9 @@ class HedgeRun:
                                   joint=not c.parity.paired_sobol, **kw)
             else:
                 scheme = "arith" if c.model == "gbm" else "log"
-                p = P.simulate_gbm(g, n, c.Y, c.r, c.sigma, scheme=scheme, norm=c.Y, fp64=fp64, **kw)
+                p = P.simulate_gbm(g, n, c.Y, c.r, c.sigma, scheme=scheme, norm=c.Y, fp64=fp64,
+                                   path_stat=self.path_stat, **kw)
+                p.stat_feature = bool(c.path_feature)
             # EO normalises BOTH prices by S0 (cell 13: _B_t = B/S0, so psi counts
             # unit bonds); the corrected default quotes the bond in S0 units.
             p.bond = g.bond(c.r, norm=c.Y if c.parity.complement_head else 1.0)
@@ -229,6 +253,11 @@ class HedgeRun:
         if self.kind == "pension":
             p_oom = D.all_reduce_scalar(float((yT < c.Y).double().sum()), device=self.device) / n if w > 1 else \
                 float((yT < c.Y).double().mean())
+        elif self.path_stat is not None:
+            # no single price level decides these payoffs: the share of paths that pay nothing
+            zero = self.v_terminal == 0
+            p_oom = D.all_reduce_scalar(float(zero.double().sum()), device=self.device) / n if w > 1 else \
+                float(zero.double().mean())
         else:
             strike = c.K / c.Y
             p_oom = D.all_reduce_scalar(float((yT < strike).double().sum()), device=self.device) / n if w > 1 else \
@@ -539,11 +568,17 @@ class HedgeRun:
                         "epochs_mse": [d.fit_mse["epochs"] for d in ind.dates],
                         "terminal_pnl_std": tp["std"], "terminal_residual_std": resid["std"],
                         "self_financing_pnl_std": sf["std"] if sf is not None else None})
-        if self.kind == "european":
+        if self.kind == "european" and self.path_stat is None:
             from .utils.reports import black_scholes
 
             bs = black_scholes(c.Y, c.K, c.r, c.sigma, c.T, c.option_type)
             summary["bs_price"], summary["bs_delta"] = bs
+        elif self.path_stat == "geomean":
+            from .analytic import geo_asian_price
+
+            # exact for the log-Euler grid the paths were simulated on
+            summary["analytic_price"] = geo_asian_price(c.Y, c.K, c.r, c.sigma, c.dt, self.grid.n_fine - 1,
+                                                        "CALL" if c.payoff.endswith("call") else "PUT")
         return RunResult(phi=phi, psi=psi, v0=ind.v0 * scale, scale=scale, holdings0=h0, induction=ind,
                          errors=error_history(ind), p_e_values=pe, terminal_pnl=tp, var=var, summary=summary,
                          timings=self.timer.summary(), config=c.to_dict(), paths=self.paths,
@@ -661,6 +696,12 @@ def european_option(S0=100.0, K=100.0, r=0.08, sigma=0.15, T=1.0, N_paths=3000, 
                     rebalancing_frequency=1 / 52, OPTION_TYPE="CALL", parity: bool = False, model: str = "gbm_log",
                     **extra) -> RunResult:
     """European call/put replication (``European Options.ipynb``; C13, C16, C34).
+
+    ``payoff=NAME`` hedges a path-dependent option on the same grid instead
+    (:data:`rphedge.ops.paths.PATH_PAYOFFS`: ``asian_call``, ``geo_asian_put``,
+    ``lookback_call``, ``asian_strike_call``, ``lookback_float_put`` ...): the
+    net then sees ``[S, running statistic]``; ``path_feature=False`` feeds it
+    ``S`` alone.
 
     Defaults are the notebook's (cell 3).  The reference driver trains the MSE
     model only (the Q99 refit is commented out) and uses the ``psi = 1 - phi``

@@ -182,7 +182,12 @@ class RunConfig:
     sv_days_per_year: float = 252.0  # corrected CIR-on-sigma: calibration steps per year (daily data)
     # extensions
     model: str = "gbm"               # gbm | gbm_log | sv_ref | heston | basket
-    payoff: str = "guarantee"        # guarantee | call | put | basket_call
+    payoff: str = "guarantee"        # guarantee | call | put | basket_call | a path-dependent option on one GBM
+                                     # asset (ops.paths.PATH_PAYOFFS): asian_call / asian_put, geo_asian_call /
+                                     # geo_asian_put, lookback_call / lookback_put (fixed strike K),
+                                     # asian_strike_call / asian_strike_put, lookback_float_call / lookback_float_put
+    path_feature: bool = True        # path-dependent payoffs: the running statistic is the net's second input
+                                     # (False: the net sees S alone - the ablation the feature is measured against)
     option_type: str = "CALL"
     mortality: bool = True
     n_assets: int = 1

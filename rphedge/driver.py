@@ -442,9 +442,10 @@ class BackwardInduction:
 def price_features(paths: Paths) -> list:
     """Indices of the features that are traded-asset prices (their hedge ratio
     has a payoff kink): every feature of a GBM / basket run, feature 0 of an
-    SV / Heston / pension run (its other features are variance / survivors)."""
+    SV / Heston / pension run (its other features are variance / survivors)
+    and of a path-statistic run (its other feature is the running statistic)."""
     nin = len(paths.features(0))
-    return list(range(nin)) if paths.kind not in ("pension", "heston", "sv") else [0]
+    return list(range(nin)) if paths.kind not in ("pension", "heston", "sv", "gbm_stat") else [0]
 
 
 def feature_norms(paths: Paths, mode: str, world: int = 1, centers=None, floor: float = 0.0) -> list:

@@ -58,6 +58,8 @@ LOSS_MSE, LOSS_PINBALL = 0, 1
 
 SIM_GBM_ARITH, SIM_GBM_LOG, SIM_SV_REF, SIM_HESTON, SIM_BASKET, SIM_MORTALITY = range(6)
 HESTON_EULER, HESTON_QE = 0, 1   # SimDesc.scheme (csrc/rph_types.h HestonScheme)
+# SimDesc.path_stat (csrc/rph_types.h PathStat): running statistic of the fine-grid GBM path
+PATH_STATS = {None: 0, "mean": 1, "geomean": 2, "max": 3, "min": 4}
 
 # Levenberg-Marquardt solver (csrc/rph_types.h LmState)
 LM_NPMAX = 192

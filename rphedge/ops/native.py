@@ -123,7 +123,7 @@ class SimDesc(C.Structure):
         ("kappa", C.c_double), ("theta", C.c_double), ("xi", C.c_double), ("rho", C.c_double),
         ("l0", C.c_double), ("lc", C.c_double), ("eta", C.c_double), ("n0", C.c_int), ("seed", C.c_uint32),
         ("out", VP), ("out2", VP), ("out3", VP), ("final_out", VP), ("final2_out", VP),
-        ("sv_tscale", C.c_double), ("scheme", C.c_int), ("pad0", C.c_int),
+        ("sv_tscale", C.c_double), ("scheme", C.c_int), ("path_stat", C.c_int),
         ("map_blk", C.c_longlong), ("map_stride", C.c_longlong),
     ]
 
@@ -159,7 +159,7 @@ def _expected_layout() -> list[int]:
         L.LM_SPEC, L.LMS_SPEC_W, L.LMS_SLOTS, L.LM_SLOT, L.LSS_LBEST, L.LSS_STOP,
         C.sizeof(S), S.path_offset.offset, S.sv1.offset, S.dims1.offset, S.sv2.offset, S.dims2.offset,
         S.s0.offset, S.chol.offset, S.dt.offset, S.inv_norm.offset, S.v0.offset, S.rho.offset, S.l0.offset,
-        S.n0.offset, S.seed.offset, S.out.offset, S.final2_out.offset, S.sv_tscale.offset, S.scheme.offset,
+        S.n0.offset, S.seed.offset, S.out.offset, S.final2_out.offset, S.sv_tscale.offset, S.scheme.offset, S.path_stat.offset,
         S.map_blk.offset, S.map_stride.offset,
         L.LAG_SLOTS,
     ]
@@ -203,7 +203,7 @@ def _bind(lib):
                                     C.c_int, VP]),
         "rph_sobol_normal": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, C.c_longlong, C.c_int, C.c_int, VP]),
         "rph_simulate": (C.c_int, [C.POINTER(SimDesc), VP]),
-        "rph_payoff": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_float, VP, VP, VP]),
+        "rph_payoff": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_float, VP, VP, VP, VP]),
         "rph_radix_hist": (C.c_int, [VP, C.c_longlong, C.c_uint32, C.c_uint32, C.c_int, C.c_int, VP, VP]),
         "rph_ipc_alloc": (C.c_int, [C.c_longlong, C.POINTER(VP), C.c_char_p]),
         "rph_ipc_open": (C.c_int, [C.c_char_p, C.POINTER(VP)]),
@@ -396,10 +396,11 @@ def pnl(desc: PnlDesc, stream=None):
 
 
 def payoff(kind: int, s: torch.Tensor, out: torch.Tensor, strike: float, nfrac=None, wts=None, na: int = 1,
-           stream=None):
+           stream=None, x=None):
+    """K7; ``x``: the per-path floating strike of kinds 4 / 5 (max(s - x, 0) / max(x - s, 0))."""
     lib = load(required=True)
     n = out.numel()
-    _check(lib.rph_payoff(kind, n, na, ptr(s), ptr(nfrac), float(strike), ptr(wts), ptr(out),
+    _check(lib.rph_payoff(kind, n, na, ptr(s), ptr(nfrac), float(strike), ptr(wts), ptr(x), ptr(out),
                           stream_handle(stream)), "rph_payoff")
 
 

@@ -70,6 +70,10 @@ class Paths:
     nfrac: torch.Tensor | None = None    # [n_coarse, n] N_t/N (pension)
     lam: torch.Tensor | None = None      # [n_coarse, n]
     nfrac_final: torch.Tensor | None = None
+    stat: torch.Tensor | None = None     # [n_coarse, n] running statistic of the fine path (kind "gbm_stat")
+    stat_final: torch.Tensor | None = None   # [n] its value at the last fine point
+    stat_kind: str | None = None         # mean | geomean | max | min
+    stat_feature: bool = True            # the statistic is a network input (False: payoff only, the ablation)
     norm: float = 1.0
     na: int = 1
     meta: dict = field(default_factory=dict)
@@ -89,6 +93,8 @@ class Paths:
             return [self.S[t], self.nfrac[t], self.lam[t]]
         if self.kind in ("heston", "sv"):
             return [self.S[t], self.vol[t]]
+        if self.kind == "gbm_stat" and self.stat_feature:
+            return [self.S[t], self.stat[t]]
         return self.prices(t)
 
 
@@ -132,15 +138,33 @@ def _desc(model, n_local, offset, grid: Grid, fp64, parity, index_map=None):
 
 def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, scheme: str = "arith",
                  norm: float = 1.0, device="cuda", offset: int = 0, fp64: bool = False, seed: int = SEED_W1,
-                 stream=None, out: Paths | None = None, index_map=None) -> Paths:
+                 stream=None, out: Paths | None = None, index_map=None, path_stat: str | None = None) -> Paths:
     """Fund/stock GBM on the fine grid, stored on the coarse grid (K1+K2+K3).
 
     ``out``: re-simulate into the buffers of an existing :class:`Paths`
     (no allocation: graph-capturable).  ``index_map``: (blk, stride) global
-    path-index map (:func:`path_indices`)."""
+    path-index map (:func:`path_indices`).
+
+    ``path_stat``: mean | geomean | max | min - a running statistic of the
+    FINE-grid path, accumulated inside the scan: at fine point j >= 1 the
+    arithmetic / geometric mean of S_1..S_j or the extreme of S_0..S_j (S_0 at
+    j = 0), stored like the price (``Paths.stat`` on the coarse dates,
+    ``Paths.stat_final`` at the last fine point, same normalisation); the
+    paths are then of kind "gbm_stat" with features [S, stat].  ``geomean``
+    needs the log scheme."""
+    if path_stat not in L.PATH_STATS:
+        raise ValueError(f"path_stat must be one of mean | geomean | max | min, got {path_stat!r}")
+    if path_stat == "geomean" and scheme != "log":
+        raise ValueError("path_stat='geomean' needs the log scheme")
+    if out is not None and out.stat_kind != path_stat:
+        raise ValueError(f"out= holds path_stat {out.stat_kind!r}, asked for {path_stat!r}")
     dev = torch.device(device)
     S = out.S if out is not None else torch.empty(grid.n_coarse, n_local, dtype=torch.float32, device=dev)
     fin = out.S_final if out is not None else torch.empty(n_local, dtype=torch.float32, device=dev)
+    A = afin = None
+    if path_stat is not None:
+        A = out.stat if out is not None else torch.empty(grid.n_coarse, n_local, dtype=torch.float32, device=dev)
+        afin = out.stat_final if out is not None else torch.empty(n_local, dtype=torch.float32, device=dev)
     if _dev_is_gpu(dev):
         from . import native
 
@@ -150,15 +174,25 @@ def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, s
         d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), dims
         d.s0[0], d.mu[0], d.sigma[0], d.inv_norm[0] = s0, mu, sigma, 1.0 / norm
         d.out, d.final_out = S.data_ptr(), fin.data_ptr()
+        if path_stat is not None:
+            d.path_stat = L.PATH_STATS[path_stat]
+            d.out2, d.final2_out = A.data_ptr(), afin.data_ptr()
         native.simulate(d, stream)
-    else:
+    elif path_stat is None:
         s_np, f_np = _cpu_gbm(grid, n_local, s0, mu, sigma, scheme, offset, seed, index_map)
         S.copy_(torch.from_numpy((s_np / norm).astype(np.float32)))
         fin.copy_(torch.from_numpy((f_np / norm).astype(np.float32)))
+    else:
+        s_np, f_np, a_np, af_np = _cpu_gbm(grid, n_local, s0, mu, sigma, scheme, offset, seed, index_map,
+                                           path_stat=path_stat)
+        S.copy_(torch.from_numpy((s_np / norm).astype(np.float32)))
+        fin.copy_(torch.from_numpy((f_np / norm).astype(np.float32)))
+        A.copy_(torch.from_numpy((a_np / norm).astype(np.float32)))
+        afin.copy_(torch.from_numpy((af_np / norm).astype(np.float32)))
     if out is not None:
         return out
-    p = Paths(kind="gbm", grid=grid, n_local=n_local, path_offset=offset, S=S, bond=grid.bond(0.0),
-              S_final=fin, norm=norm)
+    p = Paths(kind="gbm" if path_stat is None else "gbm_stat", grid=grid, n_local=n_local, path_offset=offset, S=S,
+              bond=grid.bond(0.0), S_final=fin, norm=norm, stat=A, stat_final=afin, stat_kind=path_stat)
     p.meta["index_map"] = index_map
     return p
 
@@ -302,6 +336,21 @@ def simulate_mortality(paths: Paths, l0: float, c: float, eta: float, n0: int, l
     return paths
 
 
+# path-dependent payoff name -> (path statistic, k_payoff kind): fixed strikes
+# are kinds 1 / 2 on the statistic's terminal value, floating strikes kinds
+# 4 / 5 = max(+-(S_T - stat_T), 0)
+PATH_PAYOFFS = {
+    "asian_call": ("mean", 1), "asian_put": ("mean", 2),
+    "geo_asian_call": ("geomean", 1), "geo_asian_put": ("geomean", 2),
+    "lookback_call": ("max", 1),          # max(M_T - K, 0)
+    "lookback_put": ("min", 2),           # max(K - m_T, 0)
+    "asian_strike_call": ("mean", 4),     # max(S_T - A_T, 0)
+    "asian_strike_put": ("mean", 5),      # max(A_T - S_T, 0)
+    "lookback_float_call": ("min", 4),    # S_T - m_T
+    "lookback_float_put": ("max", 5),     # M_T - S_T
+}
+
+
 def payoff(kind: str, paths: Paths, strike: float, weights=None, stream=None, out: torch.Tensor | None = None
            ) -> torch.Tensor:
     """Terminal value V_T in normalised units (K7); ``out`` reuses a buffer."""
@@ -309,7 +358,20 @@ def payoff(kind: str, paths: Paths, strike: float, weights=None, stream=None, ou
     n = paths.n_local
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=S.device)
-    code = {"guarantee": 0, "call": 1, "put": 2, "basket_call": 3}[kind]
+    x = None
+    if kind in PATH_PAYOFFS:
+        # a path-dependent payoff: a fixed strike on the statistic's terminal
+        # value (kinds 1 / 2) or the statistic as the floating strike (4 / 5)
+        want, code = PATH_PAYOFFS[kind]
+        if paths.stat_kind != want:
+            raise ValueError(f"payoff {kind!r} needs paths simulated with path_stat={want!r}, "
+                             f"got {paths.stat_kind!r}")
+        if code in (1, 2):
+            S = paths.stat_final
+        else:
+            x = paths.stat_final
+    else:
+        code = {"guarantee": 0, "call": 1, "put": 2, "basket_call": 3}[kind]
     if S.is_cuda:
         from . import native
 
@@ -320,7 +382,7 @@ def payoff(kind: str, paths: Paths, strike: float, weights=None, stream=None, ou
             if w is None:
                 w = paths.meta[key] = torch.tensor(np.asarray(weights, np.float32), device=S.device)
         native.payoff(code, S, out, strike, nfrac=paths.nfrac_final if code == 0 else None, wts=w, na=paths.na,
-                      stream=stream)
+                      stream=stream, x=x)
         return out
     if code == 0:
         y = S
@@ -330,6 +392,10 @@ def payoff(kind: str, paths: Paths, strike: float, weights=None, stream=None, ou
         out.copy_((S - strike).clamp_min(0))
     elif code == 2:
         out.copy_((strike - S).clamp_min(0))
+    elif code == 4:
+        out.copy_((S - x).clamp_min(0))
+    elif code == 5:
+        out.copy_((x - S).clamp_min(0))
     else:
         w = torch.tensor(np.asarray(weights, np.float32))
         out.copy_(((S * w[:, None]).sum(0) - strike).clamp_min(0))
@@ -345,21 +411,45 @@ def _normals(table_dims, seed, n_local, offset, dims, f32=False, index_map=None)
     return ndtri_u30_f32(np.maximum(x, 1)).astype(np.float64) if f32 else ndtri_u30_f64(x)
 
 
-def _cpu_gbm(grid, n, s0, mu, sigma, scheme, offset, seed, index_map=None):
+def _cpu_gbm(grid, n, s0, mu, sigma, scheme, offset, seed, index_map=None, path_stat=None):
+    """fp64 twin of the k_sim_scan GBM branches: (S coarse, S final), with
+    ``path_stat`` also (statistic coarse, statistic final) - the same
+    recursion as the kernel (running sum / extreme, one division per store)."""
     W = _normals(grid.n_fine, seed, n, offset, grid.n_fine, index_map=index_map)
     dt = grid.dt
     y = np.full(n, math.log(s0) if scheme == "log" else s0, dtype=np.float64)
     out = np.empty((grid.n_coarse, n))
     out[0] = s0
+    if path_stat == "geomean" and scheme != "log":
+        raise ValueError("path_stat='geomean' needs the log scheme")
+    acc = np.full(n, 0.0 if path_stat in ("mean", "geomean") else float(s0))
+    stat = np.full(n, float(s0))
+    aout = np.empty((grid.n_coarse, n))
+    aout[0] = s0
     for t in range(1, grid.n_fine):
         if scheme == "log":
             y = y + (mu - 0.5 * sigma ** 2) * dt + sigma * math.sqrt(dt) * W[:, t]
         else:
             y = y + y * (mu * dt + sigma * math.sqrt(dt) * W[:, t])
+        if path_stat is not None:
+            s = np.exp(y) if scheme == "log" else y
+            if path_stat == "mean":
+                acc = acc + s
+                stat = acc / t
+            elif path_stat == "geomean":
+                acc = acc + y
+                stat = np.exp(acc / t)
+            elif path_stat == "max":
+                acc = stat = np.maximum(acc, s)
+            else:
+                acc = stat = np.minimum(acc, s)
         if t % grid.reduction == 0 and t // grid.reduction < grid.n_coarse:
             out[t // grid.reduction] = np.exp(y) if scheme == "log" else y
+            aout[t // grid.reduction] = stat
     fin = np.exp(y) if scheme == "log" else y
-    return out, fin
+    if path_stat is None:
+        return out, fin
+    return out, fin, aout, stat
 
 
 def _u30(table_dims, seed, n_local, offset, dims, index_map=None):

@@ -415,28 +415,62 @@ __global__ __launch_bounds__(256) void k_hedge_update(const TrainDesc d, const i
 }
 
 // Supported shapes: the reference's 8-unit nets run the VALU thread-per-path
-// step kernel; 32-unit nets the MFMA step kernel (hedge_mlp_wide.hip).
-#define RPH_SHAPES(X)            \
-  X(1, 8, 1, HEAD_COMPLEMENT)    \
-  X(1, 8, 2, HEAD_FREE)          \
-  X(2, 8, 2, HEAD_FREE)          \
-  X(3, 8, 2, HEAD_FREE)          \
-  X(4, 8, 2, HEAD_FREE)          \
-  X(5, 8, 6, HEAD_FREE)          \
-  X(6, 8, 7, HEAD_FREE)
-
-#define RPH_WIDE_SHAPES(X)       \
-  X(1, 32, 1, HEAD_COMPLEMENT)   \
-  X(1, 32, 2, HEAD_FREE)         \
-  X(2, 32, 2, HEAD_FREE)         \
-  X(3, 32, 2, HEAD_FREE)         \
-  X(5, 32, 6, HEAD_FREE)
-
-static inline bool shape_is(int nin, int h, int nout, int head, int a, int b, int c, int e) {
-  return nin == a && h == b && nout == c && head == e;
+// step kernel (and are the shapes with an LM solver); 32-unit nets the MFMA
+// step kernel (hedge_mlp_wide.hip).  These two lists are the only place a
+// shape is written down: every launcher picks its instantiation from them.
+template <int NIN_, int H_, int NO_, int HEAD_>
+struct Shape {
+  static constexpr int NIN = NIN_, H = H_, NO = NO_, HEAD = HEAD_;
+  using S = NetShape<NIN_, H_, NO_, HEAD_>;
+};
+template <class... T>
+struct ShapeList {};
+template <class... A, class... B>
+constexpr ShapeList<A..., B...> operator+(ShapeList<A...>, ShapeList<B...>) {
+  return {};
 }
 
-int rph_report(const char* what, const char* msg);  // runtime.cpp: sets rph_last_error, returns -22
+using NarrowShapes = ShapeList<Shape<1, 8, 1, HEAD_COMPLEMENT>,
+                               Shape<1, 8, 2, HEAD_FREE>,
+                               Shape<2, 8, 2, HEAD_FREE>,
+                               Shape<3, 8, 2, HEAD_FREE>,
+                               Shape<4, 8, 2, HEAD_FREE>,
+                               Shape<5, 8, 6, HEAD_FREE>,
+                               Shape<6, 8, 7, HEAD_FREE>>;
+using WideShapes = ShapeList<Shape<1, 32, 1, HEAD_COMPLEMENT>,
+                             Shape<1, 32, 2, HEAD_FREE>,
+                             Shape<2, 32, 2, HEAD_FREE>,
+                             Shape<3, 32, 2, HEAD_FREE>,
+                             Shape<5, 32, 6, HEAD_FREE>>;
+using AllShapes = decltype(NarrowShapes{} + WideShapes{});
+
+// runtime.cpp: both set rph_last_error and return -22
+int rph_report(const char* what, const char* msg);
+int rph_report_shape(const char* what, int nin, int h, int nout, int head);  // "unsupported network shape ..."
+
+// Calls fn(Shape<...>{}) -> int for the first list entry equal to the runtime
+// shape and stores its result in *rc; false (fn not called) when none matches.
+// (Head-first recursion: the kernels are instantiated - and laid out in the
+// code object - in list order.)
+template <class F>
+bool match_shape(ShapeList<>, int, int, int, int, int*, F&&) {
+  return false;
+}
+template <class T, class... Rest, class F>
+bool match_shape(ShapeList<T, Rest...>, int nin, int h, int nout, int head, int* rc, F&& fn) {
+  if (nin == T::NIN && h == T::H && nout == T::NO && head == T::HEAD) {
+    *rc = fn(T{});
+    return true;
+  }
+  return match_shape(ShapeList<Rest...>{}, nin, h, nout, head, rc, fn);
+}
+
+// The launchers' form: fn's result, or the reported error for a shape not in the list.
+template <class L, class F>
+int with_shape(L list, int nin, int h, int nout, int head, const char* who, F&& fn) {
+  int rc = 0;
+  return match_shape(list, nin, h, nout, head, &rc, fn) ? rc : rph_report_shape(who, nin, h, nout, head);
+}
 
 // Host-side check of a training descriptor against what the kernels and their
 // grids assume (run before every launch: a bad shape must not reach the GPU).
@@ -473,8 +507,8 @@ inline int validate_train(const TrainDesc* d, int mode, const char* who) {
   return 0;
 }
 
-// Wide (MFMA) training-step launcher (hedge_mlp_wide.hip); returns -1 when the
-// shape is not a wide shape.
+// Wide (MFMA) training-step launcher (hedge_mlp_wide.hip); reports a shape
+// that is not a wide shape as rph_train_step's error.
 int launch_wide_step(const TrainDesc* d, int step, int epoch, const Perm& perm, hipStream_t s);
 
 }  // namespace rph

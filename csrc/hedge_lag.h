@@ -413,4 +413,10 @@ __global__ __launch_bounds__(256) void k_hedge_lag_finalize(const TrainDesc d, c
   lag_advance_seq(d, st.sc[LG_SEQ], (uint32_t)K);
 }
 
+template <class B>
+int launch_step_lag(const TrainDesc* d, int k, int epoch, const Perm& perm, hipStream_t s) {
+  hipLaunchKernelGGL((k_hedge_step_lag<B>), dim3(d->num_wgs), dim3(256), 0, s, *d, k, epoch, perm);
+  return (int)hipGetLastError();
+}
+
 }  // namespace rph

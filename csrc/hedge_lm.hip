@@ -1392,7 +1392,9 @@ struct LmKernels {
   // last LM_OUTG_TAIL passes of an lm_out_fix fit)
   using BodyOG = NarrowPairBody<NIN, H, NO, HEAD, true>;
   using S = NetShape<NIN, H, NO, HEAD>;
-  // the tile store + vectors + hand-off counters (lm_chol.h)
+  // the tile store + vectors + hand-off counters (lm_chol.h).  (6, 8, 7):
+  // P = 191, 78 tiles of the tile store = 156 KB of the CU's 160 KB; larger nets
+  // have no LM solver and fit with Adam (HipBackend.lm_supported() is False)
   static constexpr int smem() { return TileGrid<S::P>::LDS_BYTES; }
   static_assert(smem() + 128 <= 160 * 1024, "LM solve exceeds the LDS of one workgroup");
 };
@@ -1705,44 +1707,29 @@ extern "C" int rph_lm_dp_exchange(const LmDpDesc* x, double* red, int ng, int p,
   return (int)hipGetLastError();
 }
 
-#define RPH_LM_SHAPES(X)         \
-  X(1, 8, 1, HEAD_COMPLEMENT)    \
-  X(1, 8, 2, HEAD_FREE)          \
-  X(2, 8, 2, HEAD_FREE)          \
-  X(3, 8, 2, HEAD_FREE)          \
-  X(4, 8, 2, HEAD_FREE)          \
-  X(5, 8, 6, HEAD_FREE)          \
-  X(6, 8, 7, HEAD_FREE)
-// (6, 8, 7): P = 191, 78 tiles of the tile store = 156 KB of the CU's 160 KB
-// (lm_chol.h); larger nets have no LM solver and fit with Adam
-// (HipBackend.lm_supported() is False)
-
 // Geometry of the LM kernels for a shape: returns 0 and fills (P, R, NBLK)
-// or -1 for shapes without an LM solver.
+// or -1 for shapes without an LM solver (the narrow shapes have one).
 extern "C" int rph_lm_shape(int nin, int h, int nout, int head, int* p, int* r, int* nblk) {
-#define X(A, B, C, E)                                                    \
-  if (shape_is(nin, h, nout, head, A, B, C, E)) {                        \
-    using K = LmKernels<A, B, C, E>;                                     \
-    *p = K::S::P;                                                        \
-    *r = K::S::R;                                                        \
-    *nblk = LmShape<K::S::P>::NBLK;                                      \
-    return 0;                                                            \
-  }
-  RPH_LM_SHAPES(X)
-#undef X
-  return -1;
+  int rc = -1;
+  match_shape(NarrowShapes{}, nin, h, nout, head, &rc, [&](auto t) {
+    using S = typename decltype(t)::S;
+    *p = S::P;
+    *r = S::R;
+    *nblk = LmShape<S::P>::NBLK;
+    return 0;
+  });
+  return rc;
 }
 
 // Pass workgroups per CU the shape's plain pass body allows (1 or 2): the
 // host sizes the pass grid up to 256 x that (engine.lm_pass_wgs).
 extern "C" int rph_lm_pass_wps(int nin, int h, int nout, int head) {
-#define X(A, B, C, E)                                        \
-  if (shape_is(nin, h, nout, head, A, B, C, E)) {            \
-    return LmKernels<A, B, C, E>::Body::WAVES_PER_SIMD;      \
-  }
-  RPH_LM_SHAPES(X)
-#undef X
-  return 1;
+  int wps = 1;
+  match_shape(NarrowShapes{}, nin, h, nout, head, &wps, [](auto t) {
+    using T = decltype(t);
+    return (int)LmKernels<T::NIN, T::H, T::NO, T::HEAD>::Body::WAVES_PER_SIMD;
+  });
+  return wps;
 }
 
 // The descriptor of one pass: the output-Gram pass body fits once per CU
@@ -1763,47 +1750,46 @@ static LmDesc lm_pass_desc(const LmDesc& lm, const int pass) {
 // red_new when data parallel, then launches rph_lm_solve.
 extern "C" int rph_lm_eval(const TrainDesc* d, const LmDesc* lm, double* red_new, int pass, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                                           \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                  \
-    using K = LmKernels<A, B, C, E>;                                                            \
-    if (int rc = lm_validate(d, lm, K::S::P, K::S::R, LmShape<K::S::P>::NBLK, K::Body::NU)) return rc; \
-    const LmDesc lp = lm_pass_desc<K>(*lm, pass);                                               \
-    if (int rc = lm_pass_launch<A, B, C, E>(d, &lp, pass, red_new, s)) return rc;               \
-    const int ngw = lm_gram_red_wgs(LmShape<K::S::P>::NBLK * 1024, lp.gram_wgs);                \
-    /* the final evaluation built no Gram: its reduce starts past the Gram workgroups */       \
-    const int wg0 = pass == lp.passes ? ngw : 0;                                                \
-    const int rg = ngw + lm_pk_red_wgs(K::S::R, lp.num_wgs, lp.dp_fused) + lm_og_wgs(K::Body::NU) - wg0; \
-    hipLaunchKernelGGL((k_lm_reduce<K::S::P, K::S::R, K::Body::NU>), dim3(rg, lp.inst), dim3(1024), 0, s, \
-                       lp, red_new, pass, wg0);                                                 \
-    return (int)hipGetLastError();                                                              \
-  }
-  RPH_LM_SHAPES(X)
-#undef X
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        using K = LmKernels<T::NIN, T::H, T::NO, T::HEAD>;
+        constexpr int P = K::S::P, R = K::S::R, NU = K::Body::NU, NBLK = LmShape<P>::NBLK;
+        if (int rc = lm_validate(d, lm, P, R, NBLK, NU)) return rc;
+        const LmDesc lp = lm_pass_desc<K>(*lm, pass);
+        if (int rc = lm_pass_launch<T::NIN, T::H, T::NO, T::HEAD>(d, &lp, pass, red_new, s)) return rc;
+        const int ngw = lm_gram_red_wgs(NBLK * 1024, lp.gram_wgs);
+        // the final evaluation built no Gram: its reduce starts past the Gram workgroups
+        const int wg0 = pass == lp.passes ? ngw : 0;
+        const int rg = ngw + lm_pk_red_wgs(R, lp.num_wgs, lp.dp_fused) + lm_og_wgs(NU) - wg0;
+        hipLaunchKernelGGL((k_lm_reduce<P, R, NU>), dim3(rg, lp.inst), dim3(1024), 0, s, lp, red_new, pass, wg0);
+        return (int)hipGetLastError();
+      }))
+    return rc;
   return rph_report("rph_lm_eval", "no LM solver for this network shape (8-unit nets only)");
 }
 
 extern "C" int rph_lm_solve(const TrainDesc* d, const LmDesc* lm, const double* red_new, int pass, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                                                  \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                         \
-    using K = LmKernels<A, B, C, E>;                                                                   \
-    const int bytes = K::smem();                                                                       \
-    static bool attr = false;                                                                          \
-    if (!attr) {                                                                                       \
-      hipError_t e = hipFuncSetAttribute((const void*)k_lm_solve<K::S::P, K::S::R, K::Body::NU>,                   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);           \
-      if (e != hipSuccess) {                                                                           \
-        (void)hipGetLastError(); /* do not leave the error for the next runtime call */                \
-        return rph_report("rph_lm_solve", "dynamic LDS request refused");                              \
-      }                                                                                                \
-      attr = true;                                                                                     \
-    }                                                                                                  \
-    hipLaunchKernelGGL((k_lm_solve<K::S::P, K::S::R, K::Body::NU>), dim3(LM_SPEC, lm->inst), dim3(256), bytes, s, *d, *lm, \
-                       red_new, pass);                                                                 \
-    return (int)hipGetLastError();                                                                     \
-  }
-  RPH_LM_SHAPES(X)
-#undef X
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        using K = LmKernels<T::NIN, T::H, T::NO, T::HEAD>;
+        constexpr auto kernel = k_lm_solve<K::S::P, K::S::R, K::Body::NU>;
+        const int bytes = K::smem();
+        static bool attr = false;  // per shape: one instantiation of this body each
+        if (!attr) {
+          hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+          if (e != hipSuccess) {
+            (void)hipGetLastError();  // do not leave the error for the next runtime call
+            return rph_report("rph_lm_solve", "dynamic LDS request refused");
+          }
+          attr = true;
+        }
+        hipLaunchKernelGGL(kernel, dim3(LM_SPEC, lm->inst), dim3(256), bytes, s, *d, *lm, red_new, pass);
+        return (int)hipGetLastError();
+      }))
+    return rc;
   return rph_report("rph_lm_solve", "no LM solver for this network shape");
 }
 

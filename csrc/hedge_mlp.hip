@@ -488,41 +488,35 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
 // ---------------------------------------------------------------------------
 using namespace rph;
 
-#define RPH_SHAPES(X)            \
-  X(1, 8, 1, HEAD_COMPLEMENT)    \
-  X(1, 8, 2, HEAD_FREE)          \
-  X(2, 8, 2, HEAD_FREE)          \
-  X(3, 8, 2, HEAD_FREE)          \
-  X(4, 8, 2, HEAD_FREE)          \
-  X(5, 8, 6, HEAD_FREE)          \
-  X(6, 8, 7, HEAD_FREE)
-
-
 extern "C" int rph_net_nparams(int nin, int h, int nout, int head, int* p_out, int* r_out) {
-#define X(A, B, C, E)                                  \
-  if (shape_is(nin, h, nout, head, A, B, C, E)) {      \
-    *p_out = NetShape<A, B, C, E>::P;                  \
-    *r_out = NetShape<A, B, C, E>::R;                  \
-    return 0;                                          \
-  }
-  RPH_SHAPES(X)
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  int rc = -1;
+  match_shape(AllShapes{}, nin, h, nout, head, &rc, [&](auto t) {
+    using S = typename decltype(t)::S;
+    *p_out = S::P;
+    *r_out = S::R;
+    return 0;
+  });
+  return rc;
+}
+
+// The epoch's chunk permutation of a (ticketed or lagged) minibatch step.
+static Perm step_perm(const TrainDesc* d, int epoch) {
+  const uint32_t n_chunks = (uint32_t)((d->n_local + (1 << d->chunk_log2) - 1) >> d->chunk_log2);
+  return make_perm(n_chunks, d->seed, (uint32_t)epoch, d->shuffle != 0);
 }
 
 extern "C" int rph_train_step(const TrainDesc* d, int step, int epoch, void* stream) {
   if (int rc = validate_train(d, 0, "rph_train_step")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t n_chunks = (uint32_t)((d->n_local + (1 << d->chunk_log2) - 1) >> d->chunk_log2);
-  const Perm perm = make_perm(n_chunks, d->seed, (uint32_t)epoch, d->shuffle != 0);
-#define X(A, B, C, E)                                                                        \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                               \
-    hipLaunchKernelGGL((k_hedge_train_step<A, B, C, E>), dim3(d->num_wgs), dim3(256), 0, s, *d, step, epoch, perm); \
-    return (int)hipGetLastError();                                                           \
-  }
-  RPH_SHAPES(X)
-#undef X
+  const Perm perm = step_perm(d, epoch);
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_hedge_train_step<T::NIN, T::H, T::NO, T::HEAD>), dim3(d->num_wgs), dim3(256), 0, s, *d,
+                           step, epoch, perm);
+        return (int)hipGetLastError();
+      }))
+    return rc;
   return launch_wide_step(d, step, epoch, perm, s);
 }
 
@@ -530,11 +524,12 @@ extern "C" int rph_train_step(const TrainDesc* d, int step, int epoch, void* str
 extern "C" int rph_train_fit(const TrainDesc* d, int epochs, void* stream) {
   if (int rc = validate_train(d, 2, "rph_train_fit")) return rc;
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E))         \
-    return launch_fit<NarrowBody<A, B, C, E>>(d, epochs, s);
-  RPH_SHAPES(X)
-#undef X
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        return launch_fit<NarrowBody<T::NIN, T::H, T::NO, T::HEAD>>(d, epochs, s);
+      }))
+    return rc;
   return launch_wide_fit(d, epochs, s);
 }
 
@@ -542,53 +537,32 @@ extern "C" int rph_train_fit(const TrainDesc* d, int epochs, void* stream) {
 extern "C" int rph_train_lag_step(const TrainDesc* d, int k, int epoch, void* stream) {
   if (int rc = validate_train(d, 1, "rph_train_lag_step")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t n_chunks = (uint32_t)((d->n_local + (1 << d->chunk_log2) - 1) >> d->chunk_log2);
-  const Perm perm = make_perm(n_chunks, d->seed, (uint32_t)epoch, d->shuffle != 0);
-#define X(A, B, C, E)                                                                                 \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                        \
-    switch (d->variant) {                                                                             \
-      case 1: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E, 2>>), dim3(d->num_wgs), dim3(256), 0, s, \
-                                 *d, k, epoch, perm); break;                                           \
-      case 2: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E, 1, 3>>), dim3(d->num_wgs), dim3(256), 0, \
-                                 s, *d, k, epoch, perm); break;                                        \
-      case 3: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E, 2, 3>>), dim3(d->num_wgs), dim3(256), 0, \
-                                 s, *d, k, epoch, perm); break;                                        \
-      case 4: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E, 1, 1, true>>), dim3(d->num_wgs), dim3(256), \
-                                 0, s, *d, k, epoch, perm); break;                                     \
-      case 5: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E, 1, 1, false, true>>), dim3(d->num_wgs), \
-                                 dim3(256), 0, s, *d, k, epoch, perm); break;                          \
-      default: hipLaunchKernelGGL((k_hedge_step_lag<NarrowBody<A, B, C, E>>), dim3(d->num_wgs), dim3(256), 0, s, \
-                                  *d, k, epoch, perm);                                                 \
-    }                                                                                                 \
-    return (int)hipGetLastError();                                                                    \
-  }
-  RPH_SHAPES(X)
-#undef X
+  const Perm perm = step_perm(d, epoch);
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        constexpr int A = decltype(t)::NIN, B = decltype(t)::H, C = decltype(t)::NO, E = decltype(t)::HEAD;
+        switch (d->variant) {  // NarrowBody<..., WPE, PFD, LDSW, HYB>
+          case 1: return launch_step_lag<NarrowBody<A, B, C, E, 2>>(d, k, epoch, perm, s);
+          case 2: return launch_step_lag<NarrowBody<A, B, C, E, 1, 3>>(d, k, epoch, perm, s);
+          case 3: return launch_step_lag<NarrowBody<A, B, C, E, 2, 3>>(d, k, epoch, perm, s);
+          case 4: return launch_step_lag<NarrowBody<A, B, C, E, 1, 1, true>>(d, k, epoch, perm, s);
+          case 5: return launch_step_lag<NarrowBody<A, B, C, E, 1, 1, false, true>>(d, k, epoch, perm, s);
+          default: return launch_step_lag<NarrowBody<A, B, C, E>>(d, k, epoch, perm, s);
+        }
+      }))
+    return rc;
   return launch_wide_lag_step(d, k, epoch, perm, s);
 }
-
-extern "C" int rph_train_lag_finalize(const TrainDesc* d, int K, void* stream);
 
 extern "C" int rph_train_lag_finalize(const TrainDesc* d, int K, void* stream) {
   if (int rc = validate_train(d, 1, "rph_train_lag_finalize")) return rc;
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                                        \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                               \
-    using S = NetShape<A, B, C, E>;                                                          \
-    hipLaunchKernelGGL((k_hedge_lag_finalize<S::P, S::R, NARROW_NREP>), dim3(1), dim3(256), 0, s, *d, K); \
-    return (int)hipGetLastError();                                                           \
-  }
-  RPH_SHAPES(X)
-#undef X
-#define X(A, B, C, E)                                                                        \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                               \
-    using S = NetShape<A, B, C, E>;                                                          \
-    hipLaunchKernelGGL((k_hedge_lag_finalize<S::P, S::R, WIDE_NREP>), dim3(1), dim3(256), 0, s, *d, K); \
-    return (int)hipGetLastError();                                                           \
-  }
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_train_lag_finalize", [&](auto t) {
+    using T = decltype(t);
+    constexpr int NREP = T::H == 8 ? NARROW_NREP : WIDE_NREP;
+    hipLaunchKernelGGL((k_hedge_lag_finalize<T::S::P, T::S::R, NREP>), dim3(1), dim3(256), 0, s, *d, K);
+    return (int)hipGetLastError();
+  });
 }
 
 // Whole fit on the host side of the native runtime: the epochs x steps launch
@@ -617,16 +591,11 @@ extern "C" int rph_train_ticket_fit(const TrainDesc* d, int epochs, void* stream
 extern "C" int rph_train_update(const TrainDesc* d, int step, int epoch, void* stream) {
   if (!d->grad_out || !d->wts || !d->opt || !d->fit) return rph_report("rph_train_update", "null pointer");
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                                        \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                               \
-    using S = NetShape<A, B, C, E>;                                                          \
-    hipLaunchKernelGGL((k_hedge_update<S::P, S::R>), dim3(1), dim3(256), 0, s, *d, step, epoch); \
-    return (int)hipGetLastError();                                                           \
-  }
-  RPH_SHAPES(X)
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_train_update", [&](auto t) {
+    using S = typename decltype(t)::S;
+    hipLaunchKernelGGL((k_hedge_update<S::P, S::R>), dim3(1), dim3(256), 0, s, *d, step, epoch);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int rph_eval(const EvalDesc* d, void* stream) {
@@ -642,21 +611,17 @@ extern "C" int rph_eval(const EvalDesc* d, void* stream) {
   const int nhold = d->head == HEAD_COMPLEMENT ? 2 : d->nout;
   bool alias = d->nin >= nhold - 1;
   for (int k = 0; alias && k < nhold - 1; ++k) alias = d->price_t[k] == d->feat[k];
-#define X(A, B, C, E)                                                                          \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                 \
-    if constexpr (A >= NetShape<A, B, C, E>::NHOLD - 1) {                                     \
-      if (alias) {                                                                             \
-        hipLaunchKernelGGL((k_hedge_eval<A, B, C, E, true>), dim3(d->num_wgs), dim3(256), 0, s, *d); \
-        return (int)hipGetLastError();                                                         \
-      }                                                                                        \
-    }                                                                                          \
-    hipLaunchKernelGGL((k_hedge_eval<A, B, C, E, false>), dim3(d->num_wgs), dim3(256), 0, s, *d); \
-    return (int)hipGetLastError();                                                             \
-  }
-  RPH_SHAPES(X)
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_eval", [&](auto t) {
+    using T = decltype(t);
+    if constexpr (T::NIN >= T::S::NHOLD - 1) {
+      if (alias) {
+        hipLaunchKernelGGL((k_hedge_eval<T::NIN, T::H, T::NO, T::HEAD, true>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+        return (int)hipGetLastError();
+      }
+    }
+    hipLaunchKernelGGL((k_hedge_eval<T::NIN, T::H, T::NO, T::HEAD, false>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int rph_pnl(const PnlDesc* d, void* stream) {
@@ -673,13 +638,9 @@ extern "C" int rph_pnl(const PnlDesc* d, void* stream) {
   if ((long long)d->num_wgs * per_wg < d->n_local || (long long)(d->num_wgs - 1) * per_wg >= d->n_local)
     return rph_report("rph_pnl", "num_wgs does not match n_local / (256 * PNL_PPT)");
   hipStream_t s = (hipStream_t)stream;
-#define X(A, B, C, E)                                                                          \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                 \
-    hipLaunchKernelGGL((k_hedge_pnl<A, B, C, E>), dim3(d->num_wgs), dim3(256), 0, s, *d);     \
-    return (int)hipGetLastError();                                                             \
-  }
-  RPH_SHAPES(X)
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_pnl", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+    return (int)hipGetLastError();
+  });
 }

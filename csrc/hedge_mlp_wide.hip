@@ -487,6 +487,13 @@ struct WideBody {
   }
 };
 
+// Persistent per-fit kernel for the wide nets.  The 5-32-6 basket net is not
+// offered: its optimizer state (6 parameters per thread x w/m/v/best) on top of
+// the MFMA tile state spills ~1.4 KB/lane and the spilled variant gave wrong
+// results on gfx950 — that shape runs the lagged/ticketed step kernels.
+template <class S>
+constexpr bool wide_has_fit = S::R / 256 < 6;
+
 template <int NIN, int NO, int HEAD, bool F32>
 __global__ __launch_bounds__(256) void k_hedge_train_step_wide(const TrainDesc d, const int step, const int epoch,
                                                                const Perm perm) {
@@ -579,56 +586,36 @@ __global__ __launch_bounds__(256) void k_hedge_train_step_wide(const TrainDesc d
 }
 
 int launch_wide_step(const TrainDesc* d, int step, int epoch, const Perm& perm, hipStream_t s) {
-#define X(A, B, C, E)                                                                                   \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                          \
-    if (d->mfma_fp32)                                                                                   \
-      hipLaunchKernelGGL((k_hedge_train_step_wide<A, C, E, true>), dim3(d->num_wgs), dim3(256), 0, s, *d, \
-                         step, epoch, perm);                                                            \
-    else                                                                                                \
-      hipLaunchKernelGGL((k_hedge_train_step_wide<A, C, E, false>), dim3(d->num_wgs), dim3(256), 0, s, *d, \
-                         step, epoch, perm);                                                            \
-    return (int)hipGetLastError();                                                                      \
-  }
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(WideShapes{}, d->nin, d->h, d->nout, d->head, "rph_train_step", [&](auto t) {
+    using T = decltype(t);
+    if (d->mfma_fp32)
+      hipLaunchKernelGGL((k_hedge_train_step_wide<T::NIN, T::NO, T::HEAD, true>), dim3(d->num_wgs), dim3(256), 0, s,
+                         *d, step, epoch, perm);
+    else
+      hipLaunchKernelGGL((k_hedge_train_step_wide<T::NIN, T::NO, T::HEAD, false>), dim3(d->num_wgs), dim3(256), 0, s,
+                         *d, step, epoch, perm);
+    return (int)hipGetLastError();
+  });
 }
 
-// Persistent per-fit kernel for the wide nets.  The 5-32-6 basket net is not
-// offered: its optimizer state (6 parameters per thread x w/m/v/best) on top of
-// the MFMA tile state spills ~1.4 KB/lane and the spilled variant gave wrong
-// results on gfx950 — that shape runs the lagged/ticketed step kernels.
-#define RPH_WIDE_FIT_SHAPES(X)   \
-  X(1, 32, 1, HEAD_COMPLEMENT)   \
-  X(1, 32, 2, HEAD_FREE)         \
-  X(2, 32, 2, HEAD_FREE)         \
-  X(3, 32, 2, HEAD_FREE)
-
 int launch_wide_fit(const TrainDesc* d, int epochs, hipStream_t s) {
-#define X(A, B, C, E)                                                          \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                 \
-    if (d->mfma_fp32) return launch_fit<WideBody<A, C, E, true>>(d, epochs, s); \
-    return launch_fit<WideBody<A, C, E, false>>(d, epochs, s);                 \
-  }
-  RPH_WIDE_FIT_SHAPES(X)
-#undef X
-  return rph_report("rph_train_fit", "no persistent fit kernel for this network shape (use lag/ticket)");
+  return with_shape(WideShapes{}, d->nin, d->h, d->nout, d->head, "rph_train_fit", [&](auto t) {
+    using T = decltype(t);
+    if constexpr (wide_has_fit<typename T::S>) {
+      if (d->mfma_fp32) return launch_fit<WideBody<T::NIN, T::NO, T::HEAD, true>>(d, epochs, s);
+      return launch_fit<WideBody<T::NIN, T::NO, T::HEAD, false>>(d, epochs, s);
+    } else {
+      return rph_report("rph_train_fit", "no persistent fit kernel for this network shape (use lag/ticket)");
+    }
+  });
 }
 
 int launch_wide_lag_step(const TrainDesc* d, int k, int epoch, const Perm& perm, hipStream_t s) {
-#define X(A, B, C, E)                                                                                         \
-  if (shape_is(d->nin, d->h, d->nout, d->head, A, B, C, E)) {                                                \
-    if (d->mfma_fp32)                                                                                         \
-      hipLaunchKernelGGL((k_hedge_step_lag<WideBody<A, C, E, true>>), dim3(d->num_wgs), dim3(256), 0, s, *d, k, \
-                         epoch, perm);                                                                        \
-    else                                                                                                      \
-      hipLaunchKernelGGL((k_hedge_step_lag<WideBody<A, C, E, false>>), dim3(d->num_wgs), dim3(256), 0, s, *d,  \
-                         k, epoch, perm);                                                                     \
-    return (int)hipGetLastError();                                                                            \
-  }
-  RPH_WIDE_SHAPES(X)
-#undef X
-  return -1;
+  return with_shape(WideShapes{}, d->nin, d->h, d->nout, d->head, "rph_train_lag_step", [&](auto t) {
+    using T = decltype(t);
+    if (d->mfma_fp32) return launch_step_lag<WideBody<T::NIN, T::NO, T::HEAD, true>>(d, k, epoch, perm, s);
+    return launch_step_lag<WideBody<T::NIN, T::NO, T::HEAD, false>>(d, k, epoch, perm, s);
+  });
 }
 
 }  // namespace rph

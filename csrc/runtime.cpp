@@ -37,6 +37,11 @@ extern "C" const char* rph_last_error() { return g_err; }
 // descriptor validation failures from the kernel launchers (hedge_mlp.hip)
 namespace rph {
 int rph_report(const char* what, const char* msg) { return set_err(what, -22, msg); }
+int rph_report_shape(const char* what, int nin, int h, int nout, int head) {
+  char msg[128];
+  snprintf(msg, sizeof(msg), "unsupported network shape (nin %d, h %d, nout %d, head %d)", nin, h, nout, head);
+  return rph_report(what, msg);
+}
 }  // namespace rph
 
 // ---------------------------------------------------------------------------

@@ -525,7 +525,10 @@ class HipBackend:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.comm, self.world, self.rank = comm, world, rank
         self.stream = stream
-        self.P, self.R = native.net_nparams(spec.nin, spec.hidden, spec.nout, spec.head)
+        self.shape = (spec.nin, spec.hidden, spec.nout, spec.head)  # the native launchers' shape key
+        self.P, self.R = native.net_nparams(*self.shape)
+        # (P, R, Gram blocks) of the LM kernels, None without an LM solver; pass workgroups per CU
+        self._lm_shape, self._lm_wps = native.lm_shape(*self.shape), native.lm_pass_wps(*self.shape)
         assert self.P == spec.nparams
         self.batch_local, self.steps_per_epoch = _steps(self.n_local, tcfg, world)
         # narrow-body variant (csrc/hedge_mlp.hip launcher): 5 = W2 hoisted in
@@ -599,13 +602,11 @@ class HipBackend:
     def _train_desc(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, lr_t):
         n = self.native
         d = n.TrainDesc()
-        for i, f in enumerate(data.feats):
-            d.feat[i] = f.data_ptr()
-        for i, p in enumerate(data.prices_next):
-            d.price[i] = p.data_ptr()
+        n.fill_ptrs(d.feat, data.feats)
+        n.fill_ptrs(d.price, data.prices_next)
         d.target = data.target.data_ptr()
         d.wts, d.opt, d.fit = wts.data_ptr(), opt.data_ptr(), fit.data_ptr()
-        d.lr_sched = lr_t.data_ptr() if lr_t is not None else None
+        d.lr_sched = n.ptr(lr_t)
         d.slab, d.counter, d.grad_out = self.slab.data_ptr(), self.counter.data_ptr(), self.grad.data_ptr()
         d.bond = float(data.bond_next)
         d.alpha = float(self.spec.alpha)
@@ -630,10 +631,18 @@ class HipBackend:
         d.deterministic = 1 if self.tcfg.deterministic else 0
         d.mfma_fp32 = 1 if self.tcfg.mfma_fp32 else 0
         d.variant = self.variant
-        d.stamps = self.stamps.data_ptr() if self.stamps is not None else None
+        d.stamps = n.ptr(self.stamps)
         d.num_wgs = self.num_wgs
-        d.nin, d.h, d.nout, d.head = self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head
+        d.nin, d.h, d.nout, d.head = self.shape
         _set_norm(d, data)
+        return d
+
+    def _full_batch_desc(self, wts, opt, fit, data: DateData, fcfg: FitConfig, loss: int):
+        """The training descriptor of a full-batch LM launch on this rank's shard."""
+        d = self._train_desc(wts, opt, fit, data, fcfg, 0, None)
+        d.batch, d.steps_per_epoch, d.shuffle = self.n_local, 1, 0
+        d.inv_batch = 1.0 / float(self.n_local * max(self.world, 1))
+        d.loss = int(loss)
         return d
 
     def fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, poll_every: int = 0):
@@ -699,7 +708,7 @@ class HipBackend:
 
     # -- Levenberg-Marquardt ----------------------------------------------------
     def lm_supported(self) -> bool:
-        return self.native.lm_shape(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head) is not None
+        return self._lm_shape is not None
 
     def _lm_buffers(self, loss: int = L.LOSS_MSE):
         """LM state, reduced block, slabs and descriptor of this backend's fits
@@ -708,13 +717,11 @@ class HipBackend:
         pin = int(loss) == L.LOSS_PINBALL
 
         def make():
-            shp = self.native.lm_shape(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
-            if shp is None:
+            if self._lm_shape is None:
                 raise ValueError(f"no Levenberg-Marquardt solver for net {self.spec} (8-unit nets up to 174 parameters)")
-            P, R, nblk = shp
+            P, R, nblk = self._lm_shape
             t = self.tcfg
-            wps = self.native.lm_pass_wps(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
-            wps = int(os.environ.get("RPH_LM_WPS", wps))  # (env: A/B)
+            wps = int(os.environ.get("RPH_LM_WPS", self._lm_wps))  # (env: A/B)
             nw, leaf = lm_pass_schedule(self.n_local, int(os.environ.get("RPH_LM_LEAF", t.lm_leaf_paths)), wps)
             W = max(self.world, 1)
             # the global Gram subsample (every rank: gw = ns / 64 Gram workgroups,
@@ -768,15 +775,13 @@ class HipBackend:
         (without it: this rank's part of the subsample, Gram summed over ranks)."""
         g = self._lm_buffers()["gram"]
         side = allow_side and data.gram_feats is not None and data.gram_prices_next is not None
-        lm.gtarget = data.gram_target.data_ptr() if (side and data.gram_target is not None) else None
+        lm.gtarget = self.native.ptr(data.gram_target) if side else None
         if side:
             gw, blk, stride, inv = g["side"]
             if data.gram_feats[0].numel() != gw * L.LM_TILE:
                 raise ValueError(f"Gram subsample data has {data.gram_feats[0].numel()} paths, expected {gw * L.LM_TILE}")
-            for i, f in enumerate(data.gram_feats):
-                lm.gfeat[i] = f.data_ptr()
-            for i, p in enumerate(data.gram_prices_next):
-                lm.gprice[i] = p.data_ptr()
+            self.native.fill_ptrs(lm.gfeat, data.gram_feats)
+            self.native.fill_ptrs(lm.gprice, data.gram_prices_next)
         elif self.world <= 1:
             gw, blk, stride, inv = g["side"]
         else:
@@ -794,7 +799,7 @@ class HipBackend:
         when the Gram is built redundantly, else the whole reduced block)."""
         if self.world <= 1:
             return 0
-        P, _, nblk = self.native.lm_shape(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
+        P, _, nblk = self._lm_shape
         return 8 * self._lm_greg(False) if self._lm_same_gram else 8 * (nblk * 1024 + lm_tpack_len(P, nblk) + L.LM_RED - L.LM_GBLK_MAX)
 
     def _lm_greg(self, og: bool) -> int:
@@ -844,11 +849,7 @@ class HipBackend:
         lm.passes = int(fcfg.epochs)
         lm.stop_tol, lm.stop_min = float(fcfg.lm_stop_tol), max(1, int(fcfg.lm_stop_min))
         lm.lam0 = float(self.tcfg.lm_lam0 if fcfg.lm_lam0 is None else fcfg.lm_lam0)
-        d = self._train_desc(wts, opt, fit, data, fcfg, 0, None)
-        d.batch, d.steps_per_epoch, d.shuffle = self.n_local, 1, 0
-        d.inv_batch = 1.0 / float(self.n_local * max(self.world, 1))
-        d.loss = int(fcfg.loss)
-        d.quantile = float(fcfg.quantile)
+        d = self._full_batch_desc(wts, opt, fit, data, fcfg, fcfg.loss)
         n = self.native
         lm.lam_carry = float(fcfg.lm_lam_carry)
         lm.renorm = 0
@@ -905,13 +906,12 @@ class HipBackend:
         P = self.P
 
         def make():
-            _, R, nblk = self.native.lm_shape(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
+            _, R, nblk = self._lm_shape
             t, dev = self.tcfg, self.device
             # K instances in one launch: at most 256 x wps / K pass workgroups
             # each, so the whole grid is co-resident (wps workgroups per CU) and
             # a pass costs one round of workgroups, not K
-            wps = self.native.lm_pass_wps(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
-            wps = int(os.environ.get("RPH_LM_EXPLORE_WPS", wps))  # (env: A/B)
+            wps = int(os.environ.get("RPH_LM_EXPLORE_WPS", self._lm_wps))  # (env: A/B)
             nw, leaf = lm_pass_schedule(nsub, 0 if int(t.lm_leaf_paths) >= 0 else -1, wps)
             nw1 = lm_pass_schedule(nsub, 0 if int(t.lm_leaf_paths) >= 0 else -1)[0]
             if K > 1:
@@ -963,10 +963,8 @@ class HipBackend:
         lm.lam0 = float(self.tcfg.lm_lam0 if fcfg.lm_lam0 is None else fcfg.lm_lam0)
         d = type(d_main).from_buffer_copy(d_main)
         if xd is not None:
-            for i, f in enumerate(xd.feats):
-                d.feat[i] = f.data_ptr()
-            for i, p in enumerate(xd.prices_next):
-                d.price[i] = p.data_ptr()
+            self.native.fill_ptrs(d.feat, xd.feats)
+            self.native.fill_ptrs(d.price, xd.prices_next)
             d.target = xd.target.data_ptr()
         d.n_local = d.batch = nsub
         d.inv_batch = 1.0 / float(nsub)
@@ -982,7 +980,7 @@ class HipBackend:
         (every rank built the same Gram matrix): only the gradient region
         travels, [g | stats] = 200 doubles (1.6 KB), + the packed output Gram
         in the passes that build it (``og``)."""
-        P, _, nblk = self.native.lm_shape(self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head)
+        P, _, nblk = self._lm_shape
         if self.lm_mailbox is not None:
             x = self._cache.get(("lm_dp",), self.lm_mailbox.lm_desc)
             if gram:
@@ -1042,10 +1040,7 @@ class HipBackend:
             lm.inv_ns = 1.0 / float(L.LM_TILE * max(self.world, 1))
             return lm
         lm = self._cache.get(("lm_refit",), make)
-        d = self._train_desc(wts, opt, fit, data, fcfg, 0, None)
-        d.batch, d.steps_per_epoch, d.shuffle = self.n_local, 1, 0
-        d.inv_batch = 1.0 / float(self.n_local * max(self.world, 1))
-        d.loss = L.LOSS_MSE
+        d = self._full_batch_desc(wts, opt, fit, data, fcfg, L.LOSS_MSE)
         n = self.native
         if self.world <= 1:
             n.lm_fit(d, lm, b["red"], self.stream)
@@ -1121,7 +1116,8 @@ class HipBackend:
 
     def persistent_supported(self) -> bool:
         """Shapes with a persistent per-fit kernel (csrc/hedge_fit.h): every
-        8-unit net; the 32-unit nets up to 3 inputs (RPH_WIDE_FIT_SHAPES)."""
+        8-unit net; the 32-unit nets up to 3 inputs (wide_has_fit,
+        csrc/hedge_mlp_wide.hip)."""
         return self.spec.hidden == 8 or self.spec.nin <= 3
 
     def check(self):
@@ -1140,22 +1136,22 @@ class HipBackend:
         """Enqueue the self-financing P&L scan (one k_hedge_pnl launch)."""
         n = self.native
         d = n.PnlDesc()
-        f1 = data.features(1) if data.n_dates >= 1 else data.features(0)
-        for i, f in enumerate(data.features(0)):
-            d.feat[i] = f.data_ptr()
-            d.feat_ts[i] = (f1[i].data_ptr() - f.data_ptr()) // 4
-        p0, p1 = data.prices(0), data.prices(1)
-        for k, p in enumerate(p0):
-            d.price[k] = p.data_ptr()
-            d.price_ts[k] = (p1[k].data_ptr() - p.data_ptr()) // 4
+        f0, p0, p1 = data.features(0), data.prices(0), data.prices(1)
+        f1 = data.features(1) if data.n_dates >= 1 else f0
+        n.fill_ptrs(d.feat, f0)
+        n.fill_ptrs(d.price, p0)
+        for i, (a, b) in enumerate(zip(f0, f1)):
+            d.feat_ts[i] = (b.data_ptr() - a.data_ptr()) // 4
+        for k, (a, b) in enumerate(zip(p0, p1)):
+            d.price_ts[k] = (b.data_ptr() - a.data_ptr()) // 4
         d.snap = snap.data_ptr()
         d.fmu, d.fisd, d.bond = data.fmu.data_ptr(), data.fisd.data_ptr(), data.bond.data_ptr()
         d.w0, d.payoff = data.w0.data_ptr(), data.payoff.data_ptr()
-        d.pnl_out = pnl_out.data_ptr() if pnl_out is not None else None
+        d.pnl_out = n.ptr(pnl_out)
         d.stats = stats.data_ptr()
         d.alpha, d.hold_c, d.wealth0, d.has_b = float(self.spec.alpha), float(hold_c), 0.0, 1 if has_b else 0
         d.n_local, d.n_dates, d.num_wgs = self.n_local, int(data.n_dates), self.pnl_wgs()
-        d.nin, d.h, d.nout, d.head = self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head
+        d.nin, d.h, d.nout, d.head = self.shape
         assert stats.shape[0] == d.num_wgs and snap.shape[0] >= data.n_dates
         n.pnl(d, self.stream)
 
@@ -1167,24 +1163,15 @@ class HipBackend:
         _check_eval_data(self.spec, data)
         n = self.native
         d = n.EvalDesc()
-        d.snap_a = snap_a.data_ptr() if snap_a is not None else None
-        d.snap_b = snap_b.data_ptr() if snap_b is not None else None
-        for i, f in enumerate(data.feats):
-            d.feat[i] = f.data_ptr()
-        for i, p in enumerate(data.prices_now):
-            d.price_t[i] = p.data_ptr()
-        for i, p in enumerate(data.prices_next):
-            d.price_t1[i] = p.data_ptr()
-        d.target = data.target.data_ptr() if data.target is not None else None
-        d.wa = wts.data_ptr()
-        d.wb = wts_b.data_ptr() if wts_b is not None else None
-        d.g_base = g_base.data_ptr() if g_base is not None else None
-        d.v_out = v_out.data_ptr() if v_out is not None else None
+        d.snap_a, d.snap_b = n.ptr(snap_a), n.ptr(snap_b)
+        n.fill_ptrs(d.feat, data.feats)
+        n.fill_ptrs(d.price_t, data.prices_now)
+        n.fill_ptrs(d.price_t1, data.prices_next)
+        d.target = n.ptr(data.target)
+        d.wa, d.wb, d.g_base, d.v_out = wts.data_ptr(), n.ptr(wts_b), n.ptr(g_base), n.ptr(v_out)
         if hold_out is not None:
-            for k, h in enumerate(hold_out):
-                d.hold_out[k] = h.data_ptr() if h is not None else None
-        d.resid_out = resid_out.data_ptr() if resid_out is not None else None
-        d.pred1_out = pred1_out.data_ptr() if pred1_out is not None else None
+            n.fill_ptrs(d.hold_out, hold_out)
+        d.resid_out, d.pred1_out = n.ptr(resid_out), n.ptr(pred1_out)
         d.stats = stats.data_ptr()
         d.bond_t, d.bond_t1 = float(data.bond_now), float(data.bond_next)
         d.alpha = float(self.spec.alpha)
@@ -1193,7 +1180,7 @@ class HipBackend:
         if d.n_local != int(data.feats[0].numel()):
             raise ValueError(f"eval over {data.feats[0].numel()} paths with n_local {d.n_local}")
         d.num_wgs = self.eval_wgs
-        d.nin, d.h, d.nout, d.head = self.spec.nin, self.spec.hidden, self.spec.nout, self.spec.head
+        d.nin, d.h, d.nout, d.head = self.shape
         _set_norm(d, data)
         n.eval_(d, self.stream)
 

@@ -268,6 +268,12 @@ def ptr(t) -> int | None:
     return t.data_ptr()
 
 
+def fill_ptrs(arr, tensors):
+    """Fill a ``VP * N`` descriptor array from a sequence of tensors (None: a null pointer)."""
+    for i, t in enumerate(tensors):
+        arr[i] = ptr(t)
+
+
 def stream_handle(stream=None) -> int:
     """HIP stream handle of a torch stream (None: the current stream; an int is
     taken as a raw handle, 0 = the null stream)."""

@@ -180,6 +180,109 @@ def test_launcher_rejects_bad_descriptors():
         native.train_lag_fit(d, 1, stream=0)
 
 
+# shape (nin, h, nout, head) -> net_nparams (P, R), lm_shape (P, R, NBLK) or None, lm_pass_wps:
+# the one shape table of csrc/hedge_core.h, pinned to the values before it became one table
+SHAPE_TABLE = {
+    (1, 8, 1, 1): ((97, 128), (97, 128, 10), 1),
+    (1, 8, 2, 0): ((106, 128), (106, 128, 10), 2),
+    (2, 8, 2, 0): ((114, 128), (114, 128, 10), 2),
+    (3, 8, 2, 0): ((122, 128), (122, 128, 10), 1),
+    (4, 8, 2, 0): ((130, 256), (130, 256, 15), 1),
+    (5, 8, 6, 0): ((174, 256), (174, 256, 21), 1),
+    (6, 8, 7, 0): ((191, 256), (191, 256, 21), 1),
+    (1, 32, 1, 1): ((1153, 1280), None, 1),
+    (1, 32, 2, 0): ((1186, 1280), None, 1),
+    (2, 32, 2, 0): ((1218, 1280), None, 1),
+    (3, 32, 2, 0): ((1250, 1280), None, 1),
+    (5, 32, 6, 0): ((1446, 1536), None, 1),
+}
+UNKNOWN_SHAPES = [(7, 8, 2, 0), (4, 32, 2, 0), (1, 8, 1, 0), (3, 16, 2, 0)]
+
+
+def test_shape_table_pinned():
+    from rphedge.ops import native
+
+    native.load(required=True)
+    for shape, (pr, lm, wps) in SHAPE_TABLE.items():
+        assert native.net_nparams(*shape) == pr, shape
+        assert native.lm_shape(*shape) == lm, shape
+        assert native.lm_pass_wps(*shape) == wps, shape
+    for shape in UNKNOWN_SHAPES:
+        with pytest.raises(ValueError):
+            native.net_nparams(*shape)
+        assert native.lm_shape(*shape) is None, shape
+        assert native.lm_pass_wps(*shape) == 1, shape
+
+
+@pytest.mark.parametrize("shape", UNKNOWN_SHAPES)
+def test_unknown_shape_is_a_reported_error(shape):
+    """A shape outside the table on an otherwise valid descriptor: every
+    launcher reports it under its own name with the four shape numbers (no
+    kernel is launched: the dispatch fails first), never a message left over
+    from an earlier call."""
+    from rphedge.engine import PNL_PPT
+    from rphedge.ops import native
+
+    native.load(required=True)
+    nin, h, nout, head = shape
+    numbers = f"nin {nin}, h {h}, nout {nout}, head {head}"
+    buf = torch.zeros(16)
+    p = buf.data_ptr()  # non-null, never dereferenced
+
+    def stale():  # leave another launcher's validation message in the error buffer
+        bad = native.TrainDesc()
+        bad.nin, bad.h, bad.nout, bad.head = 1, 8, 2, 0
+        bad.num_wgs, bad.batch, bad.n_local, bad.steps_per_epoch = 0, 512, 4096, 8
+        with pytest.raises(RuntimeError, match="num_wgs"):
+            native.train_step(bad, 0, 0, stream=0)
+
+    def expect(who, call, text=numbers):
+        stale()
+        with pytest.raises(RuntimeError) as e:
+            call()
+        msg = str(e.value)
+        assert who in msg and text in msg and "num_wgs" not in msg, msg
+
+    d = native.TrainDesc()
+    d.nin, d.h, d.nout, d.head = shape
+    d.num_wgs, d.batch, d.n_local, d.steps_per_epoch = 16, 512, 4096, 8
+    d.alpha, d.chunk_log2 = 0.3, 6
+    d.wts = d.opt = d.fit = d.target = d.lag = d.acc = d.counter = d.slab = d.grad_out = p
+    d.fused_update = 1
+    for i in range(native.MAXIN):
+        d.feat[i], d.fisd[i] = p, 1.0
+    for k in range(native.MAXHOLD):
+        d.price[k] = p
+    expect("rph_train_step", lambda: native.train_step(d, 0, 0, stream=0))
+    expect("rph_train_lag_step", lambda: native.train_lag_step(d, 0, 0, stream=0))
+    expect("rph_train_lag_finalize", lambda: native.train_lag_finalize(d, 1, stream=0))
+    expect("rph_train_update", lambda: native.train_update(d, 0, 0, stream=0))
+
+    e = native.EvalDesc()
+    e.nin, e.h, e.nout, e.head = shape
+    e.wa = e.stats = p
+    e.n_local, e.num_wgs, e.alpha = 4096, 16, 0.3
+    for i in range(native.MAXIN):
+        e.feat[i], e.fisd[i] = p, 1.0
+    expect("rph_eval", lambda: native.eval_(e, stream=0))
+
+    q = native.PnlDesc()
+    q.nin, q.h, q.nout, q.head = shape
+    q.snap = q.stats = q.payoff = q.fmu = q.fisd = q.bond = p
+    q.n_local, q.n_dates, q.alpha = 4096, 2, 0.3
+    q.num_wgs = (q.n_local + 256 * PNL_PPT - 1) // (256 * PNL_PPT)
+    for i in range(native.MAXIN):
+        q.feat[i], q.feat_ts[i] = p, q.n_local
+    for k in range(native.MAXHOLD):
+        q.price[k], q.price_ts[k] = p, q.n_local
+    if shape == (1, 8, 1, 0):
+        # one free holding is no hedge: rph_pnl's own validation (holdings >= 2)
+        # rejects this descriptor before the dispatch, as it always did
+        expect("rph_pnl", lambda: native.pnl(q, stream=0), text="bad P&L descriptor")
+    else:
+        expect("rph_pnl", lambda: native.pnl(q, stream=0))
+
+
 def test_feature_norms_modes():
     """driver.feature_norms: per-date / pooled moments; degenerate spread
     (every path at S_0 on date 0) keeps unit scale; parity forces raw."""

@@ -8,8 +8,10 @@ Bounds (u = 2^-24; derivation in test_gpu_eval.py): per path ``|pnl - ref| <=
 8-unit nets, the wealth carried through every date; the statistics ``n x`` the
 per-path tolerance ``+ 8 u sum|terms|`` (the kernel accumulates them in fp64).
 
-Largest per-path error measured on an MI355X over every case below:
-3.0 u max|ref| per date (bound 32).
+The 32-unit nets are held to the same bound.
+
+Largest per-path error measured on an MI355X over every case below, in
+u max|ref| per date (bound 32): 7.9 for the 8-unit nets, 5.6 for the 32-unit nets.
 """
 import numpy as np
 import pytest
@@ -23,7 +25,11 @@ pytestmark = pytest.mark.gpu
 
 HOLD_C = 0.1
 # (shape, two networks per date)
-CASES = [((1, 8, 2, 0), False), ((1, 8, 1, 1), False), ((3, 8, 2, 0), True), ((5, 8, 6, 0), False)]
+CASES = [((1, 8, 2, 0), False), ((1, 8, 1, 1), False), ((3, 8, 2, 0), True), ((5, 8, 6, 0), False),
+         # the rest of the shape table (csrc/hedge_core.h): every shape reaches rph_pnl
+         ((2, 8, 2, 0), False), ((4, 8, 2, 0), False), ((6, 8, 7, 0), True),
+         ((1, 32, 1, 1), False), ((1, 32, 2, 0), False), ((2, 32, 2, 0), True), ((3, 32, 2, 0), False),
+         ((5, 32, 6, 0), False)]
 MAX_ULPS = [0.0]
 
 

@@ -28,6 +28,8 @@
 #include "hedge_lag.h"
 #include "hedge_narrow.h"
 
+#include <type_traits>
+
 namespace rph {
 
 // ---------------------------------------------------------------------------
@@ -180,7 +182,12 @@ __global__ __launch_bounds__(256) void k_hedge_train_step(const TrainDesc d, con
 // ---------------------------------------------------------------------------
 // PA: the traded-asset prices at t ARE the leading features (GBM / basket:
 // same tensors, detected by pointer on the host) - loaded once per path.
-template <int NIN, int H, int NO, int HEAD, bool PA>
+// EX: the date is an exercise date (EvalDesc.ex_kind / ex_strike): the stored
+// value is max(intrinsic, continuation) by the rule X > 0 && X >= C, and the
+// slab gains ES_EXER / ES_EXVAL / ES_CONT.  Holdings, pred1 and the residual
+// are the fitted hedge's either way (it is held over [t, t+1) by the paths
+// that go on).  The plain instantiations (EX = false) keep their code path.
+template <int NIN, int H, int NO, int HEAD, bool PA, bool EX = false>
 __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
   using S = NetShape<NIN, H, NO, HEAD>;
   constexpr int NHOLD = S::NHOLD;
@@ -277,6 +284,13 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
     for (int k = 0; k < NHOLD - 1; ++k) V = fmaf(holdv[k], cur.pt[k], V);
     V = fmaf(holdv[NHOLD - 1], d.bond_t, V);
     if (d.g_base) V = cur.gb + d.blend_c * (V - cur.gb);
+    [[maybe_unused]] float cont = V, xval = 0.f;
+    [[maybe_unused]] bool exer = false;
+    if constexpr (EX) {
+      xval = d.ex_kind == EX_PUT ? fmaxf(d.ex_strike - cur.pt[0], 0.f) : fmaxf(cur.pt[0] - d.ex_strike, 0.f);
+      exer = xval > 0.f && xval >= cont;
+      V = exer ? xval : cont;
+    }
     float res = 0.f, pred1 = 0.f;
     const float tgt = cur.tgt;
     if (has1) {
@@ -300,6 +314,11 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
       st[ES_APE] += d.target ? fabsf(res) * __frcp_rn(fmaxf(fabsf(tgt), 1e-7f)) : 0.f;
       st[ES_PRED1] += pred1;
       st[ES_COUNT] += 1.f;
+      if constexpr (EX) {
+        st[ES_EXER] += exer ? 1.f : 0.f;
+        st[ES_EXVAL] += exer ? xval : 0.f;
+        st[ES_CONT] += cont;
+      }
 #pragma unroll
       for (int k = 0; k < NHOLD; ++k) {
         st[ES_HOLD + k] += hold[k];
@@ -343,7 +362,10 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
 // ---------------------------------------------------------------------------
 constexpr int PNL_PPT = 4;
 
-template <int NIN, int H, int NO, int HEAD>
+// EX: the stopping rule of an early-exercise run (PnlDesc.ex_kind): a path is
+// frozen at its first exercise date; the workgroup still walks every date in
+// lockstep (the weights of a date are staged once for all its paths).
+template <int NIN, int H, int NO, int HEAD, bool EX = false>
 __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
   using S = NetShape<NIN, H, NO, HEAD>;
   constexpr int NHOLD = S::NHOLD;
@@ -352,7 +374,7 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
   prefetch_kernarg<sizeof(PnlDesc)>();
   RPH_DASSERT(d.n_local > 0 && d.num_wgs == (int)gridDim.x && d.snap != nullptr && d.stats != nullptr);
   __shared__ __attribute__((aligned(16))) float wl[WBOFF + S::P + 4];
-  __shared__ double sred[4][8];
+  __shared__ double sred[4][EX ? 12 : 8];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const long long base = (long long)blockIdx.x * 256 * PNL_PPT + tid;
   const bool has_b = d.has_b != 0;
@@ -382,6 +404,19 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
       for (int a = 0; a < NA; ++a) s_nxt[j][a] = d.price[a][(long long)(t + 1) * d.price_ts[a] + pidx[j]];
     }
   };
+  // early exercise: a path's exercise date (n_dates: alive), its P&L and the
+  // amount it was paid, discounted to date 0
+  [[maybe_unused]] int tau[PNL_PPT];
+  [[maybe_unused]] float pnl_ex[PNL_PPT];
+  [[maybe_unused]] double paid[PNL_PPT];
+  if constexpr (EX) {
+#pragma unroll
+    for (int j = 0; j < PNL_PPT; ++j) {
+      tau[j] = d.n_dates;
+      pnl_ex[j] = 0.f;
+      paid[j] = 0.0;
+    }
+  }
   if (d.n_dates > 0) load_date(0);
   for (int t = 0; t < d.n_dates; ++t) {
     float xc[PNL_PPT][NIN], sc_nxt[PNL_PPT][NA > 0 ? NA : 1];
@@ -406,6 +441,15 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
       isd[f] = d.fisd[t * MAXIN + f];
     }
     const float grow = (float)(d.bond[t + 1] / d.bond[t]);
+    [[maybe_unused]] bool ex_date = false;
+    [[maybe_unused]] float bond_t = 0.f, to_end = 0.f;
+    [[maybe_unused]] double disc = 0.0;
+    if constexpr (EX) {
+      ex_date = t % d.ex_every == 0;
+      bond_t = (float)d.bond[t];
+      to_end = (float)(d.bond[d.n_dates] / d.bond[t]);
+      disc = d.bond[0] / d.bond[t];
+    }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PNL_PPT; ++j) {
@@ -423,23 +467,50 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
 #pragma unroll
         for (int k = 0; k < NHOLD; ++k) hold[k] = hold[k] + d.hold_c * (hb[k] - hold[k]);
       }
+      if constexpr (EX) {
+        if (ex_date && tau[j] == d.n_dates) {
+          // continuation value of date t's network in the eval kernel's operation order
+          float c = 0.f;
+#pragma unroll
+          for (int a = 0; a < NA; ++a) c = fmaf(hold[a], s_cur[j][a], c);
+          c = fmaf(hold[NHOLD - 1], bond_t, c);
+          const float s0 = s_cur[j][0];
+          const float xv = d.ex_kind == EX_PUT ? fmaxf(d.ex_strike - s0, 0.f) : fmaxf(s0 - d.ex_strike, 0.f);
+          if (xv > 0.f && xv >= c) {
+            tau[j] = t;
+            pnl_ex[j] = (wealth[j] - xv) * to_end;
+            paid[j] = (double)xv * disc;
+            wealth[j] = wealth[j] * to_end;  // W_tau carried in the bank account to the horizon
+          }
+        }
+      }
       float w = wealth[j] * grow;
 #pragma unroll
       for (int a = 0; a < NA; ++a) {
         w = fmaf(hold[a], sc_nxt[j][a] - s_cur[j][a] * grow, w);
         s_cur[j][a] = sc_nxt[j][a];
       }
-      wealth[j] = w;
+      if constexpr (EX) wealth[j] = tau[j] == d.n_dates ? w : wealth[j];  // an exercised path is frozen
+      else wealth[j] = w;
     }
   }
   // P&L and per-workgroup fp64 statistics
   double sv = 0, sv2 = 0, sp = 0, sp2 = 0, sa = 0, cnt = 0;
   float pmin = INFINITY, pmax = -INFINITY;
+  [[maybe_unused]] double sx = 0, sxv = 0, stau = 0;
 #pragma unroll
   for (int j = 0; j < PNL_PPT; ++j) {
     const long long p = base + (long long)j * 256;
     if (p >= d.n_local) continue;
-    const float pnl = wealth[j] - d.payoff[p];
+    float pnl = wealth[j] - d.payoff[p];
+    if constexpr (EX) {
+      const bool exd = tau[j] < d.n_dates;
+      if (exd) pnl = pnl_ex[j];
+      if (d.tau_out) d.tau_out[p] = tau[j];
+      sx += exd ? 1.0 : 0.0;
+      sxv += exd ? paid[j] : (double)d.payoff[p] * (d.bond[0] / d.bond[d.n_dates]);
+      stau += (double)tau[j];
+    }
     if (d.pnl_out) d.pnl_out[p] = pnl;
     sv += wealth[j];
     sv2 += (double)wealth[j] * wealth[j];
@@ -460,6 +531,16 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
     cnt += __shfl_xor(cnt, o, 64);
     pmin = fminf(pmin, __shfl_xor(pmin, o, 64));
     pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
+    if constexpr (EX) {
+      sx += __shfl_xor(sx, o, 64);
+      sxv += __shfl_xor(sxv, o, 64);
+      stau += __shfl_xor(stau, o, 64);
+    }
+  }
+  if constexpr (EX) {
+    if (lane == 0) {
+      sred[wid][8] = sx; sred[wid][9] = sxv; sred[wid][10] = stau;
+    }
   }
   if (lane == 0) {
     sred[wid][0] = sv; sred[wid][1] = sv2; sred[wid][2] = sp; sred[wid][3] = sp2;
@@ -477,6 +558,11 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
     else if (tid == ES_COUNT) v = sum4(5);
     else if (tid == ES_RESMIN) v = fmin(fmin(sred[0][6], sred[1][6]), fmin(sred[2][6], sred[3][6]));
     else if (tid == ES_RESMAX) v = fmax(fmax(sred[0][7], sred[1][7]), fmax(sred[2][7], sred[3][7]));
+    if constexpr (EX) {
+      if (tid == ES_EXER) v = sum4(8);
+      else if (tid == ES_EXVAL) v = sum4(9);
+      else if (tid == ES_TAU) v = sum4(10);
+    }
     d.stats[(size_t)blockIdx.x * EVAL_NSTAT + tid] = v;
   }
 }
@@ -611,16 +697,26 @@ extern "C" int rph_eval(const EvalDesc* d, void* stream) {
   const int nhold = d->head == HEAD_COMPLEMENT ? 2 : d->nout;
   bool alias = d->nin >= nhold - 1;
   for (int k = 0; alias && k < nhold - 1; ++k) alias = d->price_t[k] == d->feat[k];
+  const bool ex = d->ex_kind != EX_NONE;
+  if (ex) {  // exercise date: one network, intrinsic value from price_t[0]
+    if (d->ex_kind != EX_PUT && d->ex_kind != EX_CALL) return rph_report("rph_eval", "ex_kind must be 0, 1 (put) or 2 (call)");
+    if (d->wb) return rph_report("rph_eval", "wb with ex_kind (early exercise takes one network)");
+    if (d->g_base) return rph_report("rph_eval", "g_base with ex_kind (early exercise takes one network)");
+    if (nhold < 2 || !d->price_t[0]) return rph_report("rph_eval", "price_t[0] is null with ex_kind");
+    if (!(d->ex_strike == d->ex_strike) || d->ex_strike < 0.f || d->ex_strike > 3.0e38f)
+      return rph_report("rph_eval", "ex_strike must be finite and >= 0");
+  }
   return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_eval", [&](auto t) {
     using T = decltype(t);
+    auto launch = [&](auto pa, auto exv) {
+      hipLaunchKernelGGL((k_hedge_eval<T::NIN, T::H, T::NO, T::HEAD, decltype(pa)::value, decltype(exv)::value>),
+                         dim3(d->num_wgs), dim3(256), 0, s, *d);
+      return (int)hipGetLastError();
+    };
     if constexpr (T::NIN >= T::S::NHOLD - 1) {
-      if (alias) {
-        hipLaunchKernelGGL((k_hedge_eval<T::NIN, T::H, T::NO, T::HEAD, true>), dim3(d->num_wgs), dim3(256), 0, s, *d);
-        return (int)hipGetLastError();
-      }
+      if (alias) return ex ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
     }
-    hipLaunchKernelGGL((k_hedge_eval<T::NIN, T::H, T::NO, T::HEAD, false>), dim3(d->num_wgs), dim3(256), 0, s, *d);
-    return (int)hipGetLastError();
+    return ex ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
   });
 }
 
@@ -637,10 +733,21 @@ extern "C" int rph_pnl(const PnlDesc* d, void* stream) {
   const long long per_wg = 256LL * PNL_PPT;
   if ((long long)d->num_wgs * per_wg < d->n_local || (long long)(d->num_wgs - 1) * per_wg >= d->n_local)
     return rph_report("rph_pnl", "num_wgs does not match n_local / (256 * PNL_PPT)");
+  const bool ex = d->ex_kind != EX_NONE;
+  if (ex) {  // stopping rule: one network, exercise dates t % ex_every == 0
+    if (d->ex_kind != EX_PUT && d->ex_kind != EX_CALL) return rph_report("rph_pnl", "ex_kind must be 0, 1 (put) or 2 (call)");
+    if (d->has_b) return rph_report("rph_pnl", "has_b with ex_kind (early exercise takes one network)");
+    if (d->ex_every < 1) return rph_report("rph_pnl", "ex_every must be >= 1 with ex_kind");
+    if (!(d->ex_strike == d->ex_strike) || d->ex_strike < 0.f || d->ex_strike > 3.0e38f)
+      return rph_report("rph_pnl", "ex_strike must be finite and >= 0");
+  } else if (d->tau_out) {
+    return rph_report("rph_pnl", "tau_out without ex_kind");
+  }
   hipStream_t s = (hipStream_t)stream;
   return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_pnl", [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+    if (ex) hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD, true>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+    else hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD, false>), dim3(d->num_wgs), dim3(256), 0, s, *d);
     return (int)hipGetLastError();
   });
 }

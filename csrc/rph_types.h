@@ -139,6 +139,12 @@ struct EvalDesc {
   // NetWeights blocks (may be null) - no separate copy launch per date
   NetWeights* snap_a;
   NetWeights* snap_b;
+  // early exercise at this date (ExKind; EX_NONE: V_t is the continuation
+  // value): the holder takes X = max(k - S, 0) (put) / max(S - k, 0) (call),
+  // S = price_t[0], where X > 0 and X >= the continuation value C; v_out and
+  // ES_V then hold the exercised value.  One network only (no wb / g_base).
+  int ex_kind;
+  float ex_strike;               // k, in the paths' normalised units
 };
 
 // Self-financing hedge P&L scan (k_hedge_pnl): one forward pass over the
@@ -167,6 +173,17 @@ struct PnlDesc {
   int has_b;
   int n_local, n_dates, num_wgs;
   int nin, h, nout, head;
+  // early exercise (ExKind; EX_NONE: the plain scan): at every date t with
+  // t % ex_every == 0, before the wealth update, a path still alive compares
+  // X_t (from the traded price 0) with the continuation value C_t of date t's
+  // network, sum_a h_a S_a,t + h_bond (float)B_t, by the eval kernel's rule.
+  // On exercise it pays X_t: P&L = (W_t - X_t) (float)(B_n / B_t), tau = t,
+  // and the path is frozen.  Paths never exercised end as in the plain scan,
+  // tau = n_dates.  One network only (has_b = 0).
+  int ex_kind;
+  int ex_every;
+  float ex_strike;
+  int* tau_out;                  // per-path exercise date (may be null)
 };
 
 // Levenberg-Marquardt fit (hedge_lm.hip): full-batch MSE fits of the 8-unit
@@ -376,8 +393,15 @@ constexpr int LM_SEL_MAX = 64;          // candidates (world x instances)
 enum EvalStat : int {
   ES_V = 0, ES_V2 = 1, ES_RES = 2, ES_RES2 = 3, ES_ABSRES = 4, ES_APE = 5, ES_PRED1 = 6,
   ES_COUNT = 7, ES_HOLD = 8 /* 8 entries */, ES_HOLD2 = 16 /* 8 entries */, ES_RESMIN = 24,
-  ES_RESMAX = 25
+  ES_RESMAX = 25,
+  // early exercise (zero in the plain kernels).  Eval: paths exercised at the
+  // date, sum of X over them, sum of the continuation value C over all paths.
+  // P&L scan: paths with tau < n_dates, sum of the amount paid discounted to
+  // date 0 (X_tau B_0 / B_tau, or the terminal payoff x B_0 / B_n), sum of tau.
+  ES_EXER = 26, ES_EXVAL = 27, ES_CONT = 28, ES_TAU = 29
 };
+
+enum ExKind : int { EX_NONE = 0, EX_PUT = 1, EX_CALL = 2 };
 
 struct SimDesc {
   int model;                     // SimModel

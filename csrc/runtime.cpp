@@ -66,11 +66,13 @@ extern "C" int rph_layout(long long* out, int cap) {
       OFF(EvalDesc, wa), OFF(EvalDesc, g_base), OFF(EvalDesc, v_out), OFF(EvalDesc, hold_out),
       OFF(EvalDesc, resid_out), OFF(EvalDesc, pred1_out), OFF(EvalDesc, stats), OFF(EvalDesc, bond_t),
       OFF(EvalDesc, hold_c), OFF(EvalDesc, n_local), OFF(EvalDesc, head), OFF(EvalDesc, fmu), OFF(EvalDesc, fisd),
-      OFF(EvalDesc, snap_a), OFF(EvalDesc, snap_b),
+      OFF(EvalDesc, snap_a), OFF(EvalDesc, snap_b), OFF(EvalDesc, ex_kind), OFF(EvalDesc, ex_strike),
       // PnlDesc
       (long long)sizeof(PnlDesc), OFF(PnlDesc, feat_ts), OFF(PnlDesc, price), OFF(PnlDesc, price_ts),
       OFF(PnlDesc, snap), OFF(PnlDesc, bond), OFF(PnlDesc, pnl_out), OFF(PnlDesc, stats), OFF(PnlDesc, alpha),
       OFF(PnlDesc, has_b), OFF(PnlDesc, n_dates), OFF(PnlDesc, head),
+      OFF(PnlDesc, ex_kind), OFF(PnlDesc, ex_every), OFF(PnlDesc, ex_strike), OFF(PnlDesc, tau_out),
+      (long long)ES_EXER, (long long)ES_EXVAL, (long long)ES_CONT, (long long)ES_TAU, (long long)EVAL_NSTAT,
       // LmDesc + LM state layout
       (long long)sizeof(LmDesc), OFF(LmDesc, slab_b), OFF(LmDesc, slab_g), OFF(LmDesc, num_wgs),
       OFF(LmDesc, passes), OFF(LmDesc, gram_blk), OFF(LmDesc, inv_ns), OFF(LmDesc, lam0), OFF(LmDesc, ridge), OFF(LmDesc, bias_index), OFF(LmDesc, weights_only), OFF(LmDesc, damping), OFF(LmDesc, stop_tol), OFF(LmDesc, gram_skip),

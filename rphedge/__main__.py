@@ -2,6 +2,7 @@
 
   run        --config cfg.json [--set key=value ...]   any params dict (pension, SV, European, basket)
   european   [--paths N] [--parity] [--payoff NAME] ...   European Options notebook driver (NAME: asian_call ...)
+             [--exercise bermudan [--exercise-every K]]   ... with the right to exercise at every K-th rebalancing date
   sts                                                    Single Time Step notebook driver
   sweep      [--sigmas .05,.1,...]                       volatility sweep (Multi Time Step)
   calibrate  --csv prices.csv | --synthetic               CIR calibration (Extra: Stochastic Volatility)
@@ -58,6 +59,9 @@ def main(argv=None) -> int:
     e.add_argument("--parity", action="store_true")
     e.add_argument("--payoff", default=None,
                    help="path-dependent option instead of the call: asian_call, geo_asian_call, lookback_call, ...")
+    e.add_argument("--exercise", default=None, choices=["european", "bermudan", "american"],
+                   help="bermudan: the holder may exercise at the rebalancing dates (american: at every one)")
+    e.add_argument("--exercise-every", type=int, default=None, help="bermudan: every K-th rebalancing date")
     e.add_argument("--set", nargs="*", default=[])
     e.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
     sub.add_parser("sts").add_argument("--no-parity", action="store_true")
@@ -90,6 +94,10 @@ def main(argv=None) -> int:
         extra = {k: _coerce(v) for k, v in (kv.split("=", 1) for kv in a.set)}
         if a.payoff:
             extra["payoff"] = a.payoff
+        if a.exercise:
+            extra["exercise"] = a.exercise
+        if a.exercise_every is not None:
+            extra["exercise_every"] = a.exercise_every
         res = european_option(N_paths=a.paths, rebalancing_frequency=a.rebalancing, parity=a.parity, **extra)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))

@@ -335,3 +335,54 @@ def basket_hedge_anchor(S, bond, weights, strike: float, r: float, sigma: float,
     pnl = _sf_pnl(lambda t: [S[t, a] for a in range(S.shape[1])], lambda t: hs[t], bond, n_c, price0, payoff)
     pm, ps = _moments(pnl, world)
     return {"price": float(price0.mean()), "paths": m * world, "levy_delta": {"pnl_mean": pm, "pnl_std": ps}}
+
+
+def bermudan_tree_price(S0: float, K: float, r: float, sigma: float, T: float, n_dates: int, exercise_every: int = 1,
+                        option_type: str = "PUT", steps_per_date: int = 100, exercise: str = "bermudan"):
+    """Cox-Ross-Rubinstein tree (fp64) of a call / put that may be exercised at
+    the rebalancing dates ``t`` with ``t % exercise_every == 0``, ``t = 0 ..
+    n_dates - 1``, of a grid of ``n_dates`` equal intervals over ``[0, T]`` (the
+    terminal payoff at ``T`` as always) - the exercise dates of a
+    ``exercise="bermudan"`` run, so the tree is its reference price.
+
+    ``steps_per_date`` tree steps per interval: 100 moves the at-the-money
+    European put (S0 = K = 100, r = 0.08, sigma = 0.15, T = 1) by less than
+    1e-3 when doubled.  ``exercise="european"``: no early exercise (converges
+    to Black-Scholes).
+
+    Returns ``(price, boundary)``; ``boundary[t]`` is the critical price of
+    exercise date ``t``: the largest tree node at which a put is exercised
+    (intrinsic > 0 and >= the continuation value), the smallest for a call,
+    NaN where no node is (and at the dates without the right)."""
+    n_dates, k, m = int(n_dates), int(exercise_every), int(steps_per_date)
+    if n_dates < 1 or k < 1 or m < 1:
+        raise ValueError("n_dates, exercise_every and steps_per_date must be >= 1")
+    if exercise not in ("european", "bermudan"):
+        raise ValueError(f"exercise must be european | bermudan, got {exercise!r}")
+    put = option_type.upper() == "PUT"
+    n = n_dates * m
+    dt = float(T) / n
+    u = math.exp(sigma * math.sqrt(dt))
+    disc = math.exp(-r * dt)
+    p = (math.exp(r * dt) - 1.0 / u) / (u - 1.0 / u)
+    if not 0.0 < p < 1.0:
+        raise ValueError("tree step too coarse for these r / sigma (risk-neutral probability outside (0, 1))")
+
+    def nodes(i):  # prices of step i, ascending
+        return S0 * u ** (2.0 * np.arange(i + 1, dtype=np.float64) - i)
+
+    def intrinsic(s):
+        return np.maximum(K - s, 0.0) if put else np.maximum(s - K, 0.0)
+
+    v = intrinsic(nodes(n))
+    boundary = np.full(n_dates, np.nan)
+    for i in range(n - 1, -1, -1):
+        v = disc * (p * v[1:] + (1.0 - p) * v[:-1])
+        if exercise == "bermudan" and i % m == 0 and (i // m) % k == 0:
+            s = nodes(i)
+            x = intrinsic(s)
+            ex = (x > 0.0) & (x >= v)
+            if ex.any():
+                boundary[i // m] = s[ex].max() if put else s[ex].min()
+            v = np.where(ex, x, v)
+    return float(v[0]), boundary

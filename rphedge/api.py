@@ -22,7 +22,7 @@ import torch
 from . import risk
 from .config import RunConfig, parse_params
 from .driver import BackwardInduction, InductionConfig, InductionResult, error_history, expected_value_trajectory
-from .engine import TrainConfig, gram_subsample, make_backend, set_weights
+from .engine import Exercise, TrainConfig, gram_subsample, make_backend, set_weights
 from .models import hedge_mlp as hm
 from .ops import layout as L
 from .ops import paths as P
@@ -49,6 +49,12 @@ class RunResult:
     paths: object = None                   # ops.paths.Paths of this rank (plots, C32)
     terminal_residual: dict = field(default_factory=dict)   # one-step residual at the last date (Q24)
     self_financing_pnl: dict | None = None                   # W_T - liability of the reported hedge
+    # early exercise (exercise="bermudan"; None for a European run)
+    exercise_share: float | None = None     # share of the paths exercised before T by the P&L scan's stopping rule
+    mean_exercise_date: float | None = None  # mean exercise time tau (years; T for the paths never exercised)
+    policy_value: float | None = None       # mean discounted amount paid under that rule: the policy's own price, a
+                                            # lower bound of the option value (the paths are risk-neutral)
+    tree_price: float | None = None         # binomial tree with the same exercise dates (GBM runs)
 
     def as_tuple(self):
         return self.phi, self.psi
@@ -86,6 +92,7 @@ class HedgeRun:
         self.timer = PhaseTimer(enabled=True, device=self.device)
         self.path_stat = None  # running path statistic of a path-dependent payoff (set by _kind)
         self.kind = self._kind()
+        self.exercise = self._exercise()
         self.spec = self._spec()
         self.paths = None
         self.gpaths = None  # LM Gram subsample paths (engine.gram_subsample), simulated on every rank
@@ -118,6 +125,35 @@ class HedgeRun:
         if c.payoff == "basket_call" or c.model == "basket":
             return "basket"
         return "pension"
+
+    def _exercise(self) -> Exercise | None:
+        """The early-exercise right of the run (None: European), validated."""
+        c = self.cfg
+        mode = str(c.exercise).lower()
+        if mode not in ("european", "bermudan", "american"):
+            raise ValueError(f"exercise must be european | bermudan | american, got {c.exercise!r}")
+        if mode == "european":
+            return None
+        every = int(c.exercise_every)
+        if every < 1:
+            raise ValueError(f"exercise_every must be >= 1, got {c.exercise_every!r}")
+        if mode == "american" and every != 1:
+            raise ValueError(f"exercise='american' is exercise='bermudan' with exercise_every=1, got {every}")
+        what = f"exercise={mode!r}"
+        if c.payoff in P.PATH_PAYOFFS:
+            raise ValueError(f"{what} is not available with the path-dependent payoff {c.payoff!r} "
+                             f"(the intrinsic value must depend on S_t alone: call | put)")
+        if self.kind != "european" or c.mortality:
+            raise ValueError(f"{what} is not available with a basket, pension or mortality liability (payoff "
+                             f"{c.payoff!r}, model {c.model!r}, mortality={c.mortality}): call | put on one asset")
+        if c.model not in ("gbm", "gbm_log", "heston"):
+            raise ValueError(f"{what} is not available with model {c.model!r} (gbm | gbm_log | heston)")
+        if c.train.q99:
+            raise ValueError(f"{what} is not available with q99=True (a second network, wts_b / g_base: the exercise "
+                             f"decision compares the intrinsic value with ONE network's continuation value)")
+        if c.parity.complement_head or c.parity.local_residual_pnl or c.parity.raw_features:
+            raise ValueError(f"{what} is not available with parity=True (the reference has no early exercise)")
+        return Exercise(kind=c.option_type.lower(), strike=float(c.K) / float(c.Y), every=every)
 
     def _spec(self) -> hm.NetSpec:
         c = self.cfg
@@ -375,7 +411,8 @@ class HedgeRun:
                                init_spread=str(getattr(tr, "init", "reference")) in ("spread", "aligned"),
                                init_align=self.init_align(),
                                init_shared_stream=bool(pf.shared_initializer),
-                               mean_refit=bool(tr.mean_refit) and not pf.keras_fit_only)
+                               mean_refit=bool(tr.mean_refit) and not pf.keras_fit_only,
+                               exercise=self.exercise)
         backend_q = None
         if (self.backend_kind == "hip" and self.di.world == 1 and icfg.q99 and not icfg.shared_q99_model
                 and not icfg.poll_every and tr.concurrent_q99):
@@ -579,10 +616,32 @@ class HedgeRun:
             # exact for the log-Euler grid the paths were simulated on
             summary["analytic_price"] = geo_asian_price(c.Y, c.K, c.r, c.sigma, c.dt, self.grid.n_fine - 1,
                                                         "CALL" if c.payoff.endswith("call") else "PUT")
+        xk = {}
+        if self.exercise is not None:
+            summary["exercise"] = "bermudan"
+            summary["exercise_every"] = self.exercise.every
+            # per date (t = n-2 .. 0): exercised share, mean continuation and mean exercise value
+            summary["exercise_dates"] = [
+                {"date": d.index, "share": d.exercise_share, "mean_continuation": d.mean_continuation * scale,
+                 "mean_exercise_value": d.mean_exercise_value * scale}
+                for d in ind.dates if self.induction.exercise_at(d.index) is not None]
+            if ind.pnl is not None:
+                n = ind.pnl.count
+                xk = {"exercise_share": ind.pnl.exercise_share,
+                      "mean_exercise_date": float(ind.pnl.stats[L.ES_TAU] / n) * dtc,
+                      "policy_value": ind.pnl.policy_value * scale}
+            if c.model in ("gbm", "gbm_log"):
+                from .analytic import bermudan_tree_price
+
+                xk["tree_price"], bnd = bermudan_tree_price(c.Y, c.K, c.r, c.sigma, dtc * (self.paths.n_coarse - 1),
+                                                            self.paths.n_coarse - 1, self.exercise.every,
+                                                            c.option_type)
+                summary["tree_boundary"] = [float(b) for b in bnd]
+            summary.update(xk)
         return RunResult(phi=phi, psi=psi, v0=ind.v0 * scale, scale=scale, holdings0=h0, induction=ind,
                          errors=error_history(ind), p_e_values=pe, terminal_pnl=tp, var=var, summary=summary,
                          timings=self.timer.summary(), config=c.to_dict(), paths=self.paths,
-                         terminal_residual=resid, self_financing_pnl=sf)
+                         terminal_residual=resid, self_financing_pnl=sf, **xk)
 
 
 # ---------------------------------------------------------------------------
@@ -707,6 +766,12 @@ def european_option(S0=100.0, K=100.0, r=0.08, sigma=0.15, T=1.0, N_paths=3000, 
     model only (the Q99 refit is commented out) and uses the ``psi = 1 - phi``
     head (Q13) — reproduced with ``parity=True``; the default corrected head
     learns (phi, psi) freely.
+
+    ``exercise="bermudan", exercise_every=k`` gives the holder the right to
+    exercise at every k-th rebalancing date (``"american"``: k = 1): the value
+    of such a date is max(intrinsic, continuation), the P&L scan stops a path
+    where it is exercised, and the result carries ``exercise_share``,
+    ``mean_exercise_date``, ``policy_value`` and ``tree_price``.
     """
     params = dict(Y=S0, K=K, T=T, mu=r, r=r, sigma=sigma, rebalancing=rebalancing_frequency, N=1, P=1.0, x=0.0,
                   l0=0.0, c=0.0, ita=0.0, dt=dt, n_paths=int(math.ceil(math.log2(N_paths))), payoff="call" if

@@ -189,6 +189,10 @@ class RunConfig:
     path_feature: bool = True        # path-dependent payoffs: the running statistic is the net's second input
                                      # (False: the net sees S alone - the ablation the feature is measured against)
     option_type: str = "CALL"
+    exercise: str = "european"       # european | bermudan (call / put on one asset: the holder may exercise at the
+                                     # rebalancing dates t with t % exercise_every == 0, t < the last) | american
+                                     # (= bermudan with exercise_every 1: the American option as the grid refines)
+    exercise_every: int = 1          # bermudan: every k-th rebalancing date is an exercise date
     mortality: bool = True
     n_assets: int = 1
     basket_weights: tuple = ()

@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from .engine import (MAXIN, DateData, FitConfig, PnlData, TrainConfig, fit_seed, fit_summary,
+from .engine import (MAXIN, DateData, Exercise, FitConfig, PnlData, TrainConfig, fit_seed, fit_summary,
                      geometric_lr_schedule, keras_lr_schedule, reduce_stats)
 from .models.hedge_mlp import NetSpec
 from .ops import layout as L
@@ -91,6 +91,10 @@ class InductionConfig:
     # after each Adam MSE fit: exact refit of the bond holding's output bias
     # (engine bias_refit; LM fits do it in their last solve)
     mean_refit: bool = False
+    # early exercise (engine.Exercise): the value of a date t with
+    # t % exercise.every == 0 is max(intrinsic, continuation), and the P&L scan
+    # stops a path where its holder exercises (None: European)
+    exercise: Exercise | None = None
 
 
 @dataclass
@@ -124,6 +128,28 @@ class DateResult:
         return float(math.sqrt(max(self.stats[L.ES_RES2] / n - m * m, 0.0) * n / max(n - 1, 1)))
 
     @property
+    def exercise_share(self) -> float:
+        """Share of the paths exercised (eval: at this date; P&L scan: before the horizon)."""
+        return float(self.stats[L.ES_EXER] / self.count)
+
+    @property
+    def mean_continuation(self) -> float:
+        """Mean continuation value over all paths of an exercise date (0 elsewhere)."""
+        return float(self.stats[L.ES_CONT] / self.count)
+
+    @property
+    def mean_exercise_value(self) -> float:
+        """Eval statistics of an exercise date: mean intrinsic value over the exercised paths."""
+        n = self.stats[L.ES_EXER]
+        return float(self.stats[L.ES_EXVAL] / n) if n > 0 else 0.0
+
+    @property
+    def policy_value(self) -> float:
+        """P&L-scan statistics: mean over all paths of the amount paid under
+        the scan's stopping rule, discounted to date 0 (the policy's own price)."""
+        return float(self.stats[L.ES_EXVAL] / self.count)
+
+    @property
     def errors(self) -> tuple[float, float]:
         """(mae, mape) of model1.evaluate(X1, V_{t+1}) after the MSE fit (RP:215)."""
         s = self.stats_mse if self.stats_mse is not None else self.stats
@@ -143,6 +169,7 @@ class InductionResult:
     terminal: DateResult | None = None             # one-step residual of the last date (Q24 "P&L")
     pnl: DateResult | None = None                  # self-financing P&L: stats in the eval layout (ES_RES = P&L)
     pnl_paths: torch.Tensor | None = None          # [n_local] per-path self-financing P&L (keep_paths)
+    tau: torch.Tensor | None = None                # [n_local] int32 exercise date of the P&L scan (n_dates: never)
 
 
 class BackwardInduction:
@@ -251,6 +278,15 @@ class BackwardInduction:
         self.pnl_stats = backend.new_pnl_stats()
         self.pnl_paths = torch.empty(n, dtype=torch.float32, device=dev) if keep else None
         self.pnl_done = False
+        ex = icfg.exercise
+        if ex is not None and icfg.q99:
+            raise ValueError("early exercise takes one network per date: q99=True (wts_b / g_base) is not available")
+        self.tau = torch.full((n,), self.n_dates, dtype=torch.int32, device=dev) if ex is not None else None
+
+    def exercise_at(self, t: int) -> Exercise | None:
+        """The exercise right at date t (None: the plain epilogue kernel)."""
+        ex = self.cfg.exercise
+        return ex if (ex is not None and t % int(ex.every) == 0) else None
 
     @property
     def hold_c(self) -> float:
@@ -407,12 +443,12 @@ class BackwardInduction:
                     self.eval_gram_values(t)
             else:
                 be.eval(self.w_mse, data, s_q, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
-                        snap_a=self.snap[t, 0])
+                        snap_a=self.snap[t, 0], exercise=self.exercise_at(t))
         # self-financing P&L of the reported holdings (needs every date's network)
         self.pnl_done = start == nc - 2
         if self.pnl_done:
             be.pnl(self.snap, self.pnl_data, self.pnl_stats, has_b=c.q99, hold_c=self.hold_c,
-                   pnl_out=self.pnl_paths)
+                   pnl_out=self.pnl_paths, exercise=c.exercise, tau_out=self.tau)
 
     def collect(self) -> InductionResult:
         c = self.cfg
@@ -436,6 +472,7 @@ class BackwardInduction:
             res.pnl = DateResult(index=-1, time=float(self.paths.grid.times()[-1]),
                                  stats=reduce_stats(self.pnl_stats, self.world))
             res.pnl_paths = self.pnl_paths
+            res.tau = self.tau
         return res
 
 

@@ -257,6 +257,28 @@ class PnlData:
     payoff: torch.Tensor           # [n_local] terminal liability
 
 
+@dataclass(frozen=True)
+class Exercise:
+    """Early-exercise right of a call / put on traded asset 0 (backends' ``eval`` /
+    ``pnl``): the holder takes X = max(k - S, 0) (put) or max(S - k, 0) (call)
+    where ``X > 0 and X >= C``, C the continuation value of the date's network."""
+
+    kind: str                      # "put" | "call"
+    strike: float                  # k in the paths' normalised units (K / Y)
+    every: int = 1                 # P&L scan: exercise dates are t % every == 0
+
+    def __post_init__(self):
+        if self.kind not in ("put", "call"):
+            raise ValueError(f"exercise kind must be 'put' or 'call', got {self.kind!r}")
+        if int(self.every) < 1:
+            raise ValueError(f"exercise_every must be >= 1, got {self.every!r}")
+
+    def intrinsic(self, s: torch.Tensor) -> torch.Tensor:
+        """X in the dtype of ``s`` (the strike rounded to it first, as in a descriptor)."""
+        k = torch.tensor(float(self.strike), dtype=s.dtype, device=s.device)
+        return torch.clamp(k - s, min=0) if self.kind == "put" else torch.clamp(s - k, min=0)
+
+
 PNL_PPT = 4  # paths per thread of k_hedge_pnl (csrc/hedge_mlp.hip PNL_PPT)
 GRAM_BLOCKS = 8  # global blocks of the LM Gram subsample (the largest single-node world size)
 
@@ -1132,8 +1154,10 @@ class HipBackend:
     def new_pnl_stats(self):
         return torch.zeros(self.pnl_wgs(), L.EVAL_NSTAT, dtype=torch.float64, device=self.device)
 
-    def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None):
-        """Enqueue the self-financing P&L scan (one k_hedge_pnl launch)."""
+    def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
+            exercise: Exercise | None = None, tau_out=None):
+        """Enqueue the self-financing P&L scan (one k_hedge_pnl launch);
+        ``exercise``: with the stopping rule, ``tau_out`` (int32) the exercise dates."""
         n = self.native
         d = n.PnlDesc()
         f0, p0, p1 = data.features(0), data.prices(0), data.prices(1)
@@ -1152,14 +1176,20 @@ class HipBackend:
         d.alpha, d.hold_c, d.wealth0, d.has_b = float(self.spec.alpha), float(hold_c), 0.0, 1 if has_b else 0
         d.n_local, d.n_dates, d.num_wgs = self.n_local, int(data.n_dates), self.pnl_wgs()
         d.nin, d.h, d.nout, d.head = self.shape
+        if exercise is not None:
+            d.ex_kind, d.ex_every, d.ex_strike = L.EX_KINDS[exercise.kind], int(exercise.every), float(exercise.strike)
+        if tau_out is not None:
+            assert tau_out.dtype == torch.int32 and tau_out.numel() == self.n_local
+            d.tau_out = tau_out.data_ptr()
         assert stats.shape[0] == d.num_wgs and snap.shape[0] >= data.n_dates
         n.pnl(d, self.stream)
 
     def eval(self, wts, data: DateData, stats, wts_b=None, g_base=None, blend_c=0.0, hold_c=0.0,
              v_out=None, hold_out=None, resid_out=None, pred1_out=None, snap_a=None, snap_b=None,
-             n_local: int | None = None):
+             n_local: int | None = None, exercise: Exercise | None = None):
         """k_hedge_eval over ``data`` (``n_local``: its path count when it is
-        not this backend's shard, e.g. the Gram subsample)."""
+        not this backend's shard, e.g. the Gram subsample; ``exercise``: the
+        date is an exercise date, ``v_out`` = max(intrinsic, continuation))."""
         _check_eval_data(self.spec, data)
         n = self.native
         d = n.EvalDesc()
@@ -1182,6 +1212,8 @@ class HipBackend:
         d.num_wgs = self.eval_wgs
         d.nin, d.h, d.nout, d.head = self.shape
         _set_norm(d, data)
+        if exercise is not None:
+            d.ex_kind, d.ex_strike = L.EX_KINDS[exercise.kind], float(exercise.strike)
         n.eval_(d, self.stream)
 
 
@@ -1642,13 +1674,22 @@ class TorchBackend:
     def new_pnl_stats(self):
         return torch.zeros(1, L.EVAL_NSTAT, dtype=torch.float64, device=self.device)
 
-    def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None):
+    def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
+            exercise: Exercise | None = None, tau_out=None):
         """Self-financing P&L scan (reference semantics of k_hedge_pnl)."""
         spec, dt = self.spec, torch.float32
         P = spec.nparams
         bond = data.bond.detach().cpu().double().numpy()
         fmu, fisd = data.fmu.detach().cpu(), data.fisd.detach().cpu()
         wealth = data.w0.to(dt).clone()
+        nd = int(data.n_dates)
+        if exercise is not None and has_b:
+            raise ValueError("pnl: has_b with exercise (early exercise takes one network)")
+        if exercise is None and tau_out is not None:
+            raise ValueError("pnl: tau_out without exercise")
+        tau = torch.full(wealth.shape, nd, dtype=torch.int32, device=wealth.device)
+        pnl_ex = torch.zeros_like(wealth)
+        paid = torch.zeros(wealth.shape, dtype=torch.float64, device=wealth.device)
         with torch.no_grad():
             for t in range(data.n_dates):
                 X = torch.stack([f.to(dt) for f in data.features(t)], dim=1)
@@ -1658,11 +1699,32 @@ class TorchBackend:
                     hb = torch_forward(spec, snap[t, 1, :P].to(dt), X)
                     hold = hold + hold_c * (hb - hold)
                 grow = float(bond[t + 1] / bond[t])
+                alive = tau == nd
+                if exercise is not None and t % int(exercise.every) == 0:
+                    # continuation value of date t's network vs the intrinsic value (the eval rule)
+                    now = [s.to(dt) for s in data.prices(t)]
+                    c = torch.zeros_like(wealth)
+                    for a, s0 in enumerate(now):
+                        c = c + hold[:, a] * s0
+                    c = c + hold[:, len(now)] * float(np.float32(bond[t]))
+                    x = exercise.intrinsic(now[0])
+                    ex = alive & (x > 0) & (x >= c)
+                    to_end = float(np.float32(bond[nd] / bond[t]))
+                    pnl_ex = torch.where(ex, (wealth - x) * to_end, pnl_ex)
+                    paid = torch.where(ex, x.double() * float(bond[0] / bond[t]), paid)
+                    wealth = torch.where(ex, wealth * to_end, wealth)  # W_tau in the bank account to the horizon
+                    tau = torch.where(ex, torch.full_like(tau, t), tau)
+                    alive = tau == nd
                 w = wealth * grow
                 for a, (s0, s1) in enumerate(zip(data.prices(t), data.prices(t + 1))):
                     w = w + hold[:, a] * (s1.to(dt) - s0.to(dt) * grow)
-                wealth = w
+                wealth = torch.where(alive, w, wealth) if exercise is not None else w
             pnl = wealth - data.payoff.to(dt)
+            if exercise is not None:
+                pnl = torch.where(tau < nd, pnl_ex, pnl)
+                paid = torch.where(tau < nd, paid, data.payoff.double() * float(bond[0] / bond[nd]))
+                if tau_out is not None:
+                    tau_out.copy_(tau)
             if pnl_out is not None:
                 pnl_out.copy_(pnl)
             st = torch.zeros(L.EVAL_NSTAT, dtype=torch.float64)
@@ -1671,11 +1733,13 @@ class TorchBackend:
             st[L.ES_RES], st[L.ES_RES2], st[L.ES_ABSRES] = pd.sum(), (pd * pd).sum(), pd.abs().sum()
             st[L.ES_COUNT] = pd.numel()
             st[L.ES_RESMIN], st[L.ES_RESMAX] = pd.min(), pd.max()
+            if exercise is not None:
+                st[L.ES_EXER], st[L.ES_EXVAL], st[L.ES_TAU] = (tau < nd).sum(), paid.sum(), tau.double().sum()
             stats[0].copy_(st)
 
     def eval(self, wts, data: DateData, stats, wts_b=None, g_base=None, blend_c=0.0, hold_c=0.0,
              v_out=None, hold_out=None, resid_out=None, pred1_out=None, snap_a=None, snap_b=None,
-             n_local: int | None = None):
+             n_local: int | None = None, exercise: Exercise | None = None):
         spec, dt = self.spec, torch.float32
         P = spec.nparams
         _check_eval_data(spec, data)
@@ -1701,6 +1765,15 @@ class TorchBackend:
             V = (holdv * pr0).sum(dim=1)
             if g_base is not None:
                 V = g_base + blend_c * (V - g_base)
+            if exercise is not None:
+                if wts_b is not None or g_base is not None:
+                    raise ValueError("eval: wb / g_base with exercise (early exercise takes one network)")
+                if not data.prices_now:
+                    raise ValueError("eval: price_t[0] is null with exercise")
+                cont = V
+                xval = exercise.intrinsic(data.prices_now[0].to(dt))
+                exer = (xval > 0) & (xval >= cont)
+                V = torch.where(exer, xval, cont)
             if data.prices_next:
                 pr1 = torch.stack([p.to(dt) for p in data.prices_next] +
                                   [torch.full((n,), float(data.bond_next), dtype=dt, device=X.device)], dim=1)
@@ -1734,6 +1807,10 @@ class TorchBackend:
                 st[L.ES_HOLD2 + k] = (hd[:, k] ** 2).sum()
             st[L.ES_RESMIN] = rd.min()
             st[L.ES_RESMAX] = rd.max()
+            if exercise is not None:
+                st[L.ES_EXER] = exer.sum()
+                st[L.ES_EXVAL] = torch.where(exer, xval, torch.zeros_like(xval)).double().sum()
+                st[L.ES_CONT] = cont.double().sum()
             stats[0].copy_(st)
 
 

@@ -52,6 +52,12 @@ ES_HOLD = 8
 ES_HOLD2 = 16
 ES_RESMIN = 24
 ES_RESMAX = 25
+# early exercise (zero in the plain kernels).  Eval: paths exercised at the date,
+# sum of X over them, sum of the continuation value over all paths.  P&L scan:
+# paths with tau < n_dates, sum of the amount paid discounted to date 0, sum of tau.
+ES_EXER, ES_EXVAL, ES_CONT, ES_TAU = 26, 27, 28, 29
+EX_NONE, EX_PUT, EX_CALL = 0, 1, 2   # EvalDesc / PnlDesc ex_kind (csrc/rph_types.h ExKind)
+EX_KINDS = {None: EX_NONE, "none": EX_NONE, "put": EX_PUT, "call": EX_CALL}
 
 HEAD_FREE, HEAD_COMPLEMENT = 0, 1
 LOSS_MSE, LOSS_PINBALL = 0, 1

@@ -61,7 +61,7 @@ class EvalDesc(C.Structure):
         ("hold_c", C.c_float),
         ("n_local", C.c_int), ("num_wgs", C.c_int), ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int),
         ("head", C.c_int), ("fmu", C.c_float * MAXIN), ("fisd", C.c_float * MAXIN),
-        ("snap_a", VP), ("snap_b", VP),
+        ("snap_a", VP), ("snap_b", VP), ("ex_kind", C.c_int), ("ex_strike", C.c_float),
     ]
 
     def __init__(self, *a, **kw):
@@ -78,6 +78,7 @@ class PnlDesc(C.Structure):
         ("alpha", C.c_float), ("hold_c", C.c_float), ("wealth0", C.c_float), ("has_b", C.c_int),
         ("n_local", C.c_int), ("n_dates", C.c_int), ("num_wgs", C.c_int),
         ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int), ("head", C.c_int),
+        ("ex_kind", C.c_int), ("ex_every", C.c_int), ("ex_strike", C.c_float), ("tau_out", VP),
     ]
 
 
@@ -143,10 +144,12 @@ def _expected_layout() -> list[int]:
         C.sizeof(E), E.price_t.offset, E.price_t1.offset, E.target.offset, E.wa.offset, E.g_base.offset,
         E.v_out.offset, E.hold_out.offset, E.resid_out.offset, E.pred1_out.offset, E.stats.offset,
         E.bond_t.offset, E.hold_c.offset, E.n_local.offset, E.head.offset, E.fmu.offset, E.fisd.offset,
-        E.snap_a.offset, E.snap_b.offset,
+        E.snap_a.offset, E.snap_b.offset, E.ex_kind.offset, E.ex_strike.offset,
         C.sizeof(PnlDesc), PnlDesc.feat_ts.offset, PnlDesc.price.offset, PnlDesc.price_ts.offset,
         PnlDesc.snap.offset, PnlDesc.bond.offset, PnlDesc.pnl_out.offset, PnlDesc.stats.offset,
         PnlDesc.alpha.offset, PnlDesc.has_b.offset, PnlDesc.n_dates.offset, PnlDesc.head.offset,
+        PnlDesc.ex_kind.offset, PnlDesc.ex_every.offset, PnlDesc.ex_strike.offset, PnlDesc.tau_out.offset,
+        L.ES_EXER, L.ES_EXVAL, L.ES_CONT, L.ES_TAU, L.EVAL_NSTAT,
         C.sizeof(LmDesc), LmDesc.slab_b.offset, LmDesc.slab_g.offset, LmDesc.num_wgs.offset,
         LmDesc.passes.offset, LmDesc.gram_blk.offset, LmDesc.inv_ns.offset, LmDesc.lam0.offset,
         LmDesc.ridge.offset, LmDesc.bias_index.offset, LmDesc.weights_only.offset, LmDesc.damping.offset, LmDesc.stop_tol.offset, LmDesc.gram_skip.offset,

@@ -66,6 +66,38 @@ def residual_summary(res) -> dict:
     return dict(res.terminal_pnl)
 
 
+def exercise_boundary(res) -> dict:
+    """Early-exercise boundary of a ``keep_paths`` run, from the kept values
+    and prices: per exercise date t the largest exercised S_t of a put (the
+    smallest of a call), a path counting as exercised at t where its stored
+    value is its intrinsic value, ``values[t] == X_t > 0``.  Returns
+    ``{"dates": [t ...], "times": [...], "boundary": [S ...], "tree": [...]}``
+    in price units (NaN: nobody exercises at that date; ``tree``: the binomial
+    tree's critical prices where the run reports them)."""
+    import torch
+
+    cfg, ind, paths = res.config, res.induction, res.paths
+    if str(cfg.get("exercise", "european")).lower() == "european":
+        raise ValueError("exercise_boundary needs an exercise='bermudan' run")
+    if ind.values is None or paths is None:
+        raise ValueError("exercise_boundary needs the kept values and paths (keep_paths=True)")
+    put = str(cfg["option_type"]).upper() == "PUT"
+    every = int(cfg.get("exercise_every", 1))
+    k = torch.tensor(float(cfg["K"]) / float(cfg["Y"]), dtype=torch.float32)
+    nd = paths.n_coarse - 1
+    dates = [t for t in range(nd) if t % every == 0]
+    out = []
+    for t in dates:
+        s = paths.prices(t)[0].detach().float().cpu()
+        x = torch.clamp(k - s, min=0) if put else torch.clamp(s - k, min=0)
+        ex = (x > 0) & (ind.values[t].detach().float().cpu() == x)
+        out.append(float((s[ex].max() if put else s[ex].min()) * paths.norm) if bool(ex.any()) else float("nan"))
+    tree = res.summary.get("tree_boundary")
+    dtc = paths.grid.dt_coarse
+    return {"dates": dates, "times": [t * dtc for t in dates], "boundary": out,
+            "tree": [tree[t] for t in dates] if tree is not None else None}
+
+
 def _plt():
     """matplotlib with the reference notebooks' style (C43: bmh, 20x7, font 13)."""
     import matplotlib
@@ -221,6 +253,17 @@ def plot_run(res, paths=None, out_prefix: str = "rphedge_run", max_points: int =
             ax2.legend(loc="upper right")
         axs[1].set_title("fit error per backward step")
         _save(plt, fig, files, f"{out_prefix}_trajectory.png")
+    if str(res.config.get("exercise", "european")).lower() != "european" and ind.values is not None \
+            and paths is not None:
+        eb = exercise_boundary(res)
+        fig, ax = plt.subplots()
+        ax.plot(eb["times"], eb["boundary"], marker="o", label="exercised paths")
+        if eb["tree"] is not None:
+            ax.plot(eb["times"], eb["tree"], marker="x", ls="--", label="binomial tree")
+        ax.set_title("early-exercise boundary")
+        ax.set_xlabel("t")
+        ax.legend()
+        _save(plt, fig, files, f"{out_prefix}_exercise_boundary.png")
     if paths is not None:
         files += plot_paths(paths, out_prefix=out_prefix)
     return files

@@ -233,6 +233,9 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
   constexpr int EPF = 4;
   const int stride = (int)gridDim.x * 256;
   const bool has1 = d.price_t1[0] != nullptr;
+  // folded P&L (EvalDesc.pnl_acc): a path's R is read and written by its own thread only
+  const bool pnl_on = !EX && d.pnl_acc != nullptr;
+  const bool pnl_read = pnl_on && !d.pnl_first;
   auto load_in = [&](int p, In& in) {
     in.p = p;
     in.valid = p < d.n_local;
@@ -260,6 +263,9 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
     if (p0 + EPF * stride < d.n_local) load_in(cur.p + EPF * stride, q[EPF - 1]);
     const int p = cur.p;
     const bool valid = cur.valid;
+    // R of the path: issued here, consumed after the network (one register; a
+    // slot in the load ring cost four and a wave per SIMD of occupancy)
+    const float racc = pnl_read ? d.pnl_acc[valid ? p : 0] : 0.f;
     // opaque zero offset: the weights stay in LDS and are read as broadcasts
     // every iteration instead of being hoisted into (and spilling out of) VGPRs
     uint32_t zo = 0;
@@ -306,6 +312,14 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
         if (d.hold_out[k]) d.hold_out[k][p] = hold[k];
       if (d.resid_out) d.resid_out[p] = res;
       if (d.pred1_out) d.pred1_out[p] = pred1;
+      if constexpr (!EX) {
+        if (pnl_on) {  // R_t = R_{t+1} + c_t sum_a h_a (S_a,t+1 - S_a,t g_t), the reported holdings
+          float gain = 0.f;
+#pragma unroll
+          for (int k = 0; k < NHOLD - 1; ++k) gain = fmaf(hold[k], cur.pt1[k] - cur.pt[k] * d.pnl_grow, gain);
+          d.pnl_acc[p] = fmaf(d.pnl_carry, gain, racc);
+        }
+      }
       st[ES_V] += V;
       st[ES_V2] += V * V;
       st[ES_RES] += res;
@@ -567,6 +581,67 @@ __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Finish of the P&L folded into the backward induction (PnlFinishDesc,
+// EvalDesc.pnl_acc): the evals of dates n-1 .. 0 left R_0 per path; one thread
+// per path closes W_T = W_0 c + R_0, P&L = W_T - liability.  Workgroup w owns
+// the paths [w, w + 1) x 256 PNL_PPT and writes the statistics row k_hedge_pnl
+// writes for them (collect() / reduce_stats read either).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pnl_finish(const PnlFinishDesc d) {
+  RPH_DASSERT(d.n_local > 0 && d.num_wgs == (int)gridDim.x && d.acc != nullptr && d.stats != nullptr);
+  __shared__ double sred[4][8];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long long base = (long long)blockIdx.x * 256 * PNL_PPT + tid;
+  double sv = 0, sv2 = 0, sp = 0, sp2 = 0, sa = 0, cnt = 0;
+  float pmin = INFINITY, pmax = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < PNL_PPT; ++j) {
+    const long long p = base + (long long)j * 256;
+    if (p >= d.n_local) continue;
+    const float w = fmaf(d.w0[p], d.carry, d.acc[p]);
+    const float pnl = w - d.payoff[p];
+    if (d.pnl_out) d.pnl_out[p] = pnl;
+    sv += w;
+    sv2 += (double)w * w;
+    sp += pnl;
+    sp2 += (double)pnl * pnl;
+    sa += fabsf(pnl);
+    cnt += 1.0;
+    pmin = fminf(pmin, pnl);
+    pmax = fmaxf(pmax, pnl);
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    sv += __shfl_xor(sv, o, 64);
+    sv2 += __shfl_xor(sv2, o, 64);
+    sp += __shfl_xor(sp, o, 64);
+    sp2 += __shfl_xor(sp2, o, 64);
+    sa += __shfl_xor(sa, o, 64);
+    cnt += __shfl_xor(cnt, o, 64);
+    pmin = fminf(pmin, __shfl_xor(pmin, o, 64));
+    pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
+  }
+  if (lane == 0) {
+    sred[wid][0] = sv; sred[wid][1] = sv2; sred[wid][2] = sp; sred[wid][3] = sp2;
+    sred[wid][4] = sa; sred[wid][5] = cnt; sred[wid][6] = pmin; sred[wid][7] = pmax;
+  }
+  __syncthreads();
+  if (tid < EVAL_NSTAT) {
+    double v = 0.0;
+    auto sum4 = [&](int k) { return (sred[0][k] + sred[1][k]) + (sred[2][k] + sred[3][k]); };
+    if (tid == ES_V) v = sum4(0);
+    else if (tid == ES_V2) v = sum4(1);
+    else if (tid == ES_RES) v = sum4(2);
+    else if (tid == ES_RES2) v = sum4(3);
+    else if (tid == ES_ABSRES) v = sum4(4);
+    else if (tid == ES_COUNT) v = sum4(5);
+    else if (tid == ES_RESMIN) v = fmin(fmin(sred[0][6], sred[1][6]), fmin(sred[2][6], sred[3][6]));
+    else if (tid == ES_RESMAX) v = fmax(fmax(sred[0][7], sred[1][7]), fmax(sred[2][7], sred[3][7]));
+    d.stats[(size_t)blockIdx.x * EVAL_NSTAT + tid] = v;
+  }
+}
+
 }  // namespace rph
 
 // ---------------------------------------------------------------------------
@@ -706,6 +781,13 @@ extern "C" int rph_eval(const EvalDesc* d, void* stream) {
     if (!(d->ex_strike == d->ex_strike) || d->ex_strike < 0.f || d->ex_strike > 3.0e38f)
       return rph_report("rph_eval", "ex_strike must be finite and >= 0");
   }
+  if (d->pnl_acc) {  // folded P&L: the term needs both price rows; the stopping rule of an exercise run does not fold
+    if (ex) return rph_report("rph_eval", "pnl_acc with ex_kind (the early-exercise P&L is the forward scan)");
+    for (int k = 0; k < nhold - 1; ++k)
+      if (!d->price_t[k] || !d->price_t1[k]) return rph_report("rph_eval", "pnl_acc needs price_t and price_t1");
+    if (!(fabsf(d->pnl_grow) <= 3.0e38f) || !(fabsf(d->pnl_carry) <= 3.0e38f))
+      return rph_report("rph_eval", "pnl_grow / pnl_carry must be finite");
+  }
   return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_eval", [&](auto t) {
     using T = decltype(t);
     auto launch = [&](auto pa, auto exv) {
@@ -748,6 +830,22 @@ extern "C" int rph_pnl(const PnlDesc* d, void* stream) {
     using T = decltype(t);
     if (ex) hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD, true>), dim3(d->num_wgs), dim3(256), 0, s, *d);
     else hipLaunchKernelGGL((k_hedge_pnl<T::NIN, T::H, T::NO, T::HEAD, false>), dim3(d->num_wgs), dim3(256), 0, s, *d);
+    return (int)hipGetLastError();
+  });
+}
+
+// Finish of the folded P&L (the evals accumulated PnlFinishDesc.acc): the grid
+// and statistics rows of rph_pnl, so either fills the same slab.
+extern "C" int rph_pnl_finish(const PnlFinishDesc* d, void* stream) {
+  if (!d->acc || !d->w0 || !d->payoff || !d->stats || d->n_local < 1)
+    return rph_report("rph_pnl_finish", "bad P&L finish descriptor");
+  if (!(fabsf(d->carry) <= 3.0e38f)) return rph_report("rph_pnl_finish", "carry must be finite");
+  const long long per_wg = 256LL * PNL_PPT;
+  if ((long long)d->num_wgs * per_wg < d->n_local || (long long)(d->num_wgs - 1) * per_wg >= d->n_local)
+    return rph_report("rph_pnl_finish", "num_wgs does not match n_local / (256 * PNL_PPT)");
+  hipStream_t s = (hipStream_t)stream;
+  return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_pnl_finish", [&](auto) {
+    hipLaunchKernelGGL(k_pnl_finish, dim3(d->num_wgs), dim3(256), 0, s, *d);
     return (int)hipGetLastError();
   });
 }

@@ -66,9 +66,11 @@ RPH_INLINE long long sim_gidx(const SimDesc& d, int p) {
 // FINE-grid path, monitored at the fine points j = 1..t (max / min also at
 // j = 0), kept in a register beside the state and stored to out2 / final2_out
 // exactly like the price.  STAT = 0 is the plain scan.
-template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
-__global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
+// The scan of workgroup `blk` of descriptor d (k_sim_scan: the whole grid one
+// descriptor; k_sim_scan_pair: two descriptors side by side).
+template <typename Real, bool ALIGNED, int MODEL, int STAT>
+RPH_INLINE void sim_scan_block(const SimDesc& d, const int blk) {
+  const int p = blk * 256 + threadIdx.x;
   if (!ALIGNED && p >= d.n_local) return;
   const long long gp = sim_gidx(d, p);
   const uint32_t g = gray_code((uint64_t)gp);
@@ -254,6 +256,22 @@ __global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
   }
 }
 
+template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
+__global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
+  sim_scan_block<Real, ALIGNED, MODEL, STAT>(d, (int)blockIdx.x);
+}
+
+// Two scans of the same instantiation in one launch: workgroups [0, split) run
+// descriptor a, the rest descriptor b (the run's paths and the LM Gram
+// subsample: the second is a few workgroups of pure Sobol / ndtri latency,
+// which hide beside the first instead of following it on an empty GPU).  Every
+// thread runs sim_scan_block exactly as in a launch of its own.
+template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
+__global__ __launch_bounds__(256) void k_sim_scan_pair(const SimDesc a, const SimDesc b, const int split) {
+  if ((int)blockIdx.x < split) sim_scan_block<Real, ALIGNED, MODEL, STAT>(a, (int)blockIdx.x);
+  else sim_scan_block<Real, ALIGNED, MODEL, STAT>(b, (int)blockIdx.x - split);
+}
+
 // ---------------------------------------------------------------------------
 // Correlated basket (log-Euler), Cholesky factor in kernel args (uniform).
 // Sobol dimension of (step t, asset a) = a * n_fine + t  (column 0 unused, Q8).
@@ -386,32 +404,45 @@ extern "C" int rph_sobol_normal(void* out, int n, int d, const uint32_t* sv, con
   return (int)hipGetLastError();
 }
 
+// One scan instantiation: descriptor d alone, or d and d2 side by side in one
+// grid (d2 non-null: k_sim_scan_pair; the mortality scan is never paired).
+template <typename Real, bool AL, int MODEL, int STAT = 0>
+static void launch_scan_kernel(const SimDesc* d, const SimDesc* d2, hipStream_t s) {
+  const int split = grid_for(d->n_local);
+  if constexpr (MODEL != SIM_MORTALITY) {
+    if (d2) {
+      hipLaunchKernelGGL((k_sim_scan_pair<Real, AL, MODEL, STAT>), dim3(split + grid_for(d2->n_local)), dim3(256), 0, s,
+                         *d, *d2, split);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT>), dim3(split), dim3(256), 0, s, *d);
+}
+
 // GBM scans with a running path statistic (SimDesc.path_stat, validated by rph_simulate)
 template <typename Real, bool AL, int MODEL>
-static int launch_scan_stat(const SimDesc* d, hipStream_t s) {
-  const dim3 grid(grid_for(d->n_local)), block(256);
+static int launch_scan_stat(const SimDesc* d, const SimDesc* d2, hipStream_t s) {
   switch (d->path_stat) {
-    case STAT_MEAN: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MEAN>), grid, block, 0, s, *d); break;
-    case STAT_GEOMEAN: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_LOG, STAT_GEOMEAN>), grid, block, 0, s, *d); break;
-    case STAT_MAX: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MAX>), grid, block, 0, s, *d); break;
-    case STAT_MIN: hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT_MIN>), grid, block, 0, s, *d); break;
+    case STAT_MEAN: launch_scan_kernel<Real, AL, MODEL, STAT_MEAN>(d, d2, s); break;
+    case STAT_GEOMEAN: launch_scan_kernel<Real, AL, SIM_GBM_LOG, STAT_GEOMEAN>(d, d2, s); break;
+    case STAT_MAX: launch_scan_kernel<Real, AL, MODEL, STAT_MAX>(d, d2, s); break;
+    case STAT_MIN: launch_scan_kernel<Real, AL, MODEL, STAT_MIN>(d, d2, s); break;
     default: return -1;
   }
   return (int)hipGetLastError();
 }
 
 template <typename Real, bool AL>
-static int launch_scan(const SimDesc* d, hipStream_t s) {
-  const dim3 grid(grid_for(d->n_local)), block(256);
+static int launch_scan(const SimDesc* d, hipStream_t s, const SimDesc* d2 = nullptr) {
   if (d->path_stat != STAT_NONE)
-    return d->model == SIM_GBM_LOG ? launch_scan_stat<Real, AL, SIM_GBM_LOG>(d, s)
-                                   : launch_scan_stat<Real, AL, SIM_GBM_ARITH>(d, s);
+    return d->model == SIM_GBM_LOG ? launch_scan_stat<Real, AL, SIM_GBM_LOG>(d, d2, s)
+                                   : launch_scan_stat<Real, AL, SIM_GBM_ARITH>(d, d2, s);
   switch (d->model) {
-    case SIM_GBM_ARITH: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_ARITH>), grid, block, 0, s, *d); break;
-    case SIM_GBM_LOG: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_GBM_LOG>), grid, block, 0, s, *d); break;
-    case SIM_SV_REF: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_SV_REF>), grid, block, 0, s, *d); break;
-    case SIM_HESTON: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_HESTON>), grid, block, 0, s, *d); break;
-    case SIM_MORTALITY: hipLaunchKernelGGL((k_sim_scan<Real, AL, SIM_MORTALITY>), grid, block, 0, s, *d); break;
+    case SIM_GBM_ARITH: launch_scan_kernel<Real, AL, SIM_GBM_ARITH>(d, d2, s); break;
+    case SIM_GBM_LOG: launch_scan_kernel<Real, AL, SIM_GBM_LOG>(d, d2, s); break;
+    case SIM_SV_REF: launch_scan_kernel<Real, AL, SIM_SV_REF>(d, d2, s); break;
+    case SIM_HESTON: launch_scan_kernel<Real, AL, SIM_HESTON>(d, d2, s); break;
+    case SIM_MORTALITY: launch_scan_kernel<Real, AL, SIM_MORTALITY>(d, nullptr, s); break;
     default: return -1;
   }
   return (int)hipGetLastError();
@@ -432,23 +463,53 @@ static int launch_basket(const SimDesc* d, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+static int validate_sim(const SimDesc* d, const char* who) {
+  if (d->map_blk < 0 || (d->map_blk > 0 && d->map_stride < d->map_blk)) return rph_report(who, "bad path-index map");
+  if (d->path_stat < STAT_NONE || d->path_stat > STAT_MIN) return rph_report(who, "path_stat outside 0..4");
+  if (d->path_stat != STAT_NONE) {
+    if (d->model != SIM_GBM_ARITH && d->model != SIM_GBM_LOG) return rph_report(who, "path statistics need a GBM model");
+    if (!d->out2) return rph_report(who, "path statistic without an out2 buffer");
+    if (d->path_stat == STAT_GEOMEAN && d->model != SIM_GBM_LOG)
+      return rph_report(who, "geomean needs the log scheme (SIM_GBM_LOG)");
+  }
+  return 0;
+}
+
+// (aligned: every wave's 64 paths are one aligned range of global indices)
+static bool sim_aligned(const SimDesc* d) {
+  return (d->n_local % 256 == 0) && (d->path_offset % 64 == 0) &&
+         (d->map_blk == 0 || (d->map_blk % 64 == 0 && d->map_stride % 64 == 0));
+}
+
 extern "C" int rph_simulate(const SimDesc* d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (d->map_blk < 0 || (d->map_blk > 0 && d->map_stride < d->map_blk)) return rph_report("rph_simulate", "bad path-index map");
-  if (d->path_stat < STAT_NONE || d->path_stat > STAT_MIN) return rph_report("rph_simulate", "path_stat outside 0..4");
-  if (d->path_stat != STAT_NONE) {
-    if (d->model != SIM_GBM_ARITH && d->model != SIM_GBM_LOG)
-      return rph_report("rph_simulate", "path statistics need a GBM model");
-    if (!d->out2) return rph_report("rph_simulate", "path statistic without an out2 buffer");
-    if (d->path_stat == STAT_GEOMEAN && d->model != SIM_GBM_LOG)
-      return rph_report("rph_simulate", "geomean needs the log scheme (SIM_GBM_LOG)");
-  }
-  // (aligned: every wave's 64 paths are one aligned range of global indices)
-  const bool aligned = (d->n_local % 256 == 0) && (d->path_offset % 64 == 0) &&
-                       (d->map_blk == 0 || (d->map_blk % 64 == 0 && d->map_stride % 64 == 0));
+  if (int rc = validate_sim(d, "rph_simulate")) return rc;
+  const bool aligned = sim_aligned(d);
   if (d->model == SIM_BASKET) return aligned ? launch_basket<true>(d, s) : launch_basket<false>(d, s);
   if (d->fp64) return aligned ? launch_scan<double, true>(d, s) : launch_scan<double, false>(d, s);
   return aligned ? launch_scan<float, true>(d, s) : launch_scan<float, false>(d, s);
+}
+
+// Scans a and b (independent outputs) in ONE launch when both select the same
+// k_sim_scan instantiation (Real, ALIGNED, MODEL, STAT), a's workgroups first;
+// otherwise - and for the basket and mortality kernels - two launches, as two
+// rph_simulate calls.  *merged (may be null) tells which it was.
+extern "C" int rph_simulate_pair(const SimDesc* a, const SimDesc* b, int* merged, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (merged) *merged = 0;
+  if (int rc = validate_sim(a, "rph_simulate_pair")) return rc;
+  if (int rc = validate_sim(b, "rph_simulate_pair")) return rc;
+  const bool aligned = sim_aligned(a);
+  const bool same = a->model == b->model && (a->fp64 != 0) == (b->fp64 != 0) && a->path_stat == b->path_stat &&
+                    aligned == sim_aligned(b) && a->model != SIM_BASKET && a->model != SIM_MORTALITY &&
+                    (long long)grid_for(a->n_local) + grid_for(b->n_local) <= 0x7fffffffLL;
+  if (!same) {
+    if (int rc = rph_simulate(a, stream)) return rc;
+    return rph_simulate(b, stream);
+  }
+  if (merged) *merged = 1;
+  if (a->fp64) return aligned ? launch_scan<double, true>(a, s, b) : launch_scan<double, false>(a, s, b);
+  return aligned ? launch_scan<float, true>(a, s, b) : launch_scan<float, false>(a, s, b);
 }
 
 extern "C" int rph_payoff(int kind, int n, int na, const float* s, const float* nfrac, float strike,

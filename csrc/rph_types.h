@@ -145,6 +145,35 @@ struct EvalDesc {
   // ES_V then hold the exercised value.  One network only (no wb / g_base).
   int ex_kind;
   float ex_strike;               // k, in the paths' normalised units
+  // self-financing P&L folded into the backward induction (null: off).  The
+  // wealth recursion W_{t+1} = W_t g_t + sum_a h_a,t (S_a,t+1 - S_a,t g_t),
+  // g_t = fp32(B_{t+1} / B_t), is linear in W_0: W_T = W_0 c_{-1} + R_0 with
+  //   R_t = R_{t+1} + c_t sum_a h_a,t (S_a,t+1 - S_a,t g_t),  c_t = prod_{s>t} g_s
+  // and the induction visits the dates in that order.  The final eval of date
+  // t adds its term to pnl_acc[p] from the reported holdings and the prices it
+  // has loaded anyway (price_t / price_t1 are required); k_pnl_finish closes
+  // the recursion after date 0.  Not with ex_kind (the stopping rule runs forward).
+  float* pnl_acc;                // R, [n_local]
+  float pnl_grow;                // g_t
+  float pnl_carry;               // c_t (the fp64 product of the fp32 g_s, rounded once)
+  int pnl_first;                 // 1: the first accumulated date - R is written, never read
+  int pad_pnl;
+};
+
+// Finish of the folded P&L (k_pnl_finish): one thread per path,
+//   W_T = w0[p] carry + acc[p],  P&L = W_T - payoff[p],
+// statistics in the layout and workgroup count of k_hedge_pnl (ES_V = W_T,
+// ES_RES = P&L; 256 * PNL_PPT paths per workgroup).
+struct PnlFinishDesc {
+  const float* acc;              // R_0 (EvalDesc.pnl_acc after the eval of date 0)
+  const float* w0;               // initial wealth per path (values[0])
+  const float* payoff;           // terminal liability per path
+  float* pnl_out;                // per-path P&L (may be null)
+  double* stats;                 // [num_wgs][EVAL_NSTAT]
+  float carry;                   // c_{-1} = prod of every g_s
+  int n_local, num_wgs;
+  int nin, h, nout, head;        // the run's network shape (validated like rph_pnl's; the kernel is shape-free)
+  int pad0;
 };
 
 // Self-financing hedge P&L scan (k_hedge_pnl): one forward pass over the

@@ -67,6 +67,11 @@ extern "C" int rph_layout(long long* out, int cap) {
       OFF(EvalDesc, resid_out), OFF(EvalDesc, pred1_out), OFF(EvalDesc, stats), OFF(EvalDesc, bond_t),
       OFF(EvalDesc, hold_c), OFF(EvalDesc, n_local), OFF(EvalDesc, head), OFF(EvalDesc, fmu), OFF(EvalDesc, fisd),
       OFF(EvalDesc, snap_a), OFF(EvalDesc, snap_b), OFF(EvalDesc, ex_kind), OFF(EvalDesc, ex_strike),
+      OFF(EvalDesc, pnl_acc), OFF(EvalDesc, pnl_grow), OFF(EvalDesc, pnl_carry), OFF(EvalDesc, pnl_first),
+      // PnlFinishDesc
+      (long long)sizeof(PnlFinishDesc), OFF(PnlFinishDesc, w0), OFF(PnlFinishDesc, payoff), OFF(PnlFinishDesc, pnl_out),
+      OFF(PnlFinishDesc, stats), OFF(PnlFinishDesc, carry), OFF(PnlFinishDesc, n_local), OFF(PnlFinishDesc, num_wgs),
+      OFF(PnlFinishDesc, nin), OFF(PnlFinishDesc, head),
       // PnlDesc
       (long long)sizeof(PnlDesc), OFF(PnlDesc, feat_ts), OFF(PnlDesc, price), OFF(PnlDesc, price_ts),
       OFF(PnlDesc, snap), OFF(PnlDesc, bond), OFF(PnlDesc, pnl_out), OFF(PnlDesc, stats), OFF(PnlDesc, alpha),

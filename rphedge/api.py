@@ -189,13 +189,23 @@ class HedgeRun:
         the global Gram subsample simulated on this rank (:meth:`gram_paths`)."""
         c = self.cfg
         vt_out = self.v_terminal if into is not None else None
+        tr = c.train
+        lm = str(tr.optimizer).lower() == "lm"
+        # LM fits on the GPU, single-asset scans (GBM, SV / Heston): the run's
+        # scan and the Gram subsample's go out in ONE launch (k_sim_scan_pair) -
+        # the subsample is a few workgroups of pure latency
+        pair = [] if (lm and self.kind == "european" and self.device.type == "cuda") else None
         with self.timer.phase("simulate"):
-            p = self._simulate_paths(self.n_local, self.offset, None, into)
-            v_t = self._payoff(p, vt_out)
-            tr = c.train
-            if str(tr.optimizer).lower() == "lm":
+            p = self._simulate_paths(self.n_local, self.offset, None, into, defer=pair)
+            if lm:
                 ns, blk, stride = gram_subsample(self.n_total, tr.lm_gram_paths)
-                self.gpaths = self._simulate_paths(ns, 0, (blk, stride), self.gpaths if into is not None else None)
+                self.gpaths = self._simulate_paths(ns, 0, (blk, stride), self.gpaths if into is not None else None,
+                                                   defer=pair)
+            if pair is not None:
+                from .ops import native
+                native.simulate_pair(pair[0], pair[1], self.stream)
+            v_t = self._payoff(p, vt_out)
+            if lm:
                 if self._q_lm():
                     # pinball LM fits: the subsample's own terminal values (its
                     # later targets come from the date-boundary evaluations)
@@ -227,12 +237,18 @@ class HedgeRun:
             return P.payoff("basket_call", p, c.K / c.Y, weights=w, stream=self.stream, out=out)
         return P.payoff("guarantee", p, c.K, stream=self.stream, out=out)
 
-    def _simulate_paths(self, n: int, offset: int, index_map, into: P.Paths | None) -> P.Paths:
+    def _simulate_paths(self, n: int, offset: int, index_map, into: P.Paths | None, defer: list | None = None
+                        ) -> P.Paths:
         """One model's coarse-grid paths for ``n`` paths from global index
-        ``offset`` (``index_map``: the Gram subsample's global blocks)."""
+        ``offset`` (``index_map``: the Gram subsample's global blocks;
+        ``defer``: single-asset scans only - collect the scan's descriptor
+        instead of launching it, :func:`rphedge.ops.paths.simulate_gbm`)."""
         c, g, dev = self.cfg, self.grid, self.device
         fp64 = c.dtype == "fp64"
         kw = dict(device=dev, offset=offset, stream=self.stream, out=into, index_map=index_map)
+        if defer is not None:
+            assert self.kind == "european"
+            kw["defer"] = defer
         if self.kind == "european":
             if c.model == "heston":
                 p = P.simulate_sv(g, n, c.Y, c.r, c.v0, model="heston", kappa=c.kappa, theta=c.theta, xi=c.xi,

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .engine import (MAXIN, DateData, Exercise, FitConfig, PnlData, TrainConfig, fit_seed, fit_summary,
-                     geometric_lr_schedule, keras_lr_schedule, reduce_stats)
+                     geometric_lr_schedule, keras_lr_schedule, pnl_fold_factors, reduce_stats)
 from .models.hedge_mlp import NetSpec
 from .ops import layout as L
 from .ops.paths import Paths
@@ -278,6 +278,16 @@ class BackwardInduction:
         self.pnl_stats = backend.new_pnl_stats()
         self.pnl_paths = torch.empty(n, dtype=torch.float32, device=dev) if keep else None
         self.pnl_done = False
+        # a backend with pnl_finish (HipBackend) folds the P&L of a full,
+        # non-exercise run into the final eval of every date (R per path,
+        # EvalDesc.pnl_acc) and finishes it with one small kernel; the forward
+        # scan be.pnl stays for the early-exercise runs (a forward stopping
+        # rule) and the backends without the fold
+        self.pnl_fold = hasattr(backend, "pnl_finish") and icfg.exercise is None and nd >= 1
+        if self.pnl_fold:
+            self.pnl_grow, self.pnl_carry, self.pnl_carry_all = pnl_fold_factors(paths.bond)
+            # (NaN-filled: the first accumulated date must write it, never read it)
+            self.pnl_acc = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
         ex = icfg.exercise
         if ex is not None and icfg.q99:
             raise ValueError("early exercise takes one network per date: q99=True (wts_b / g_base) is not available")
@@ -391,8 +401,13 @@ class BackwardInduction:
         nc = self.paths.n_coarse
         start = nc - 2 if start is None else int(start)
         self.ran = list(range(start, -1, -1))
+        # the P&L needs every date: a resumed run (start below the last date) reports none
+        self.pnl_done = start == nc - 2
+        fold = self.pnl_fold and self.pnl_done
         for t in self.ran:
             first = t == nc - 2
+            pnl_kw = dict(pnl_acc=self.pnl_acc, pnl_grow=float(self.pnl_grow[t]), pnl_carry=float(self.pnl_carry[t]),
+                          pnl_first=first) if fold else {}
             data = self.date_data(t)
             if not c.carry_optimizer and c.warm_start and not first:
                 self.opt_mse.copy_(self.opt_init)
@@ -438,15 +453,17 @@ class BackwardInduction:
                            seed=fit_seed(c.seed, t, 1), poll_every=c.poll_every)
                 be.eval(self.w_mse, data, s_q, wts_b=self.w_q, g_base=self.gbuf, blend_c=c.cost_of_capital,
                         hold_c=self.hold_c, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
-                        snap_a=self.snap[t, 0], snap_b=self.snap[t, 1])
+                        snap_a=self.snap[t, 0], snap_b=self.snap[t, 1], **pnl_kw)
                 if self.gvalues is not None:
                     self.eval_gram_values(t)
             else:
                 be.eval(self.w_mse, data, s_q, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
-                        snap_a=self.snap[t, 0], exercise=self.exercise_at(t))
+                        snap_a=self.snap[t, 0], exercise=self.exercise_at(t), **pnl_kw)
         # self-financing P&L of the reported holdings (needs every date's network)
-        self.pnl_done = start == nc - 2
-        if self.pnl_done:
+        if fold:
+            be.pnl_finish(self.pnl_acc, self.values[0], self.values[nc - 1], float(self.pnl_carry_all),
+                          self.pnl_stats, pnl_out=self.pnl_paths)
+        elif self.pnl_done:
             be.pnl(self.snap, self.pnl_data, self.pnl_stats, has_b=c.q99, hold_c=self.hold_c,
                    pnl_out=self.pnl_paths, exercise=c.exercise, tau_out=self.tau)
 

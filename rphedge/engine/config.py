@@ -3,6 +3,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from ..ops import layout as L
@@ -207,6 +208,20 @@ class PnlData:
     fisd: torch.Tensor             # [n_dates, MAXIN]
     w0: torch.Tensor               # [n_local] initial wealth (the fitted V_0)
     payoff: torch.Tensor           # [n_local] terminal liability
+
+
+def pnl_fold_factors(bond) -> tuple:
+    """Per-date factors of the P&L folded into the backward induction
+    (``HipBackend.eval(pnl_acc=...)`` / ``pnl_finish``), from the bank account
+    ``bond`` ([n_dates + 1]): ``(grow, carry, carry_all)`` with ``grow[t] = g_t
+    = fp32(B_{t+1} / B_t)`` (the factor k_hedge_pnl applies), ``carry[t] = c_t``
+    = the fp64 product of the fp32 ``g_s`` over ``s > t``, rounded once to
+    fp32 (``c_{n-1} = 1``), and ``carry_all = c_{-1}``, the product of every
+    ``g_s``: W_T = W_0 c_{-1} + sum_t c_t sum_a h_a,t (S_a,t+1 - S_a,t g_t)."""
+    b = np.asarray(bond, np.float64)
+    g = (b[1:] / b[:-1]).astype(np.float32)
+    tail = np.concatenate([np.cumprod(g[::-1].astype(np.float64))[::-1], [1.0]])  # tail[t] = prod_{s >= t} g_s
+    return g, tail[1:].astype(np.float32), np.float32(tail[0])
 
 
 @dataclass(frozen=True)

@@ -637,12 +637,38 @@ class HipBackend(StateBlocks):
         assert stats.shape[0] == d.num_wgs and snap.shape[0] >= data.n_dates
         n.pnl(d, self.stream)
 
+    def pnl_finish(self, acc, w0, payoff, carry: float, stats, pnl_out=None):
+        """Enqueue k_pnl_finish after the eval of date 0 of a run whose evals
+        accumulated ``acc`` (``eval(pnl_acc=...)``): W_T = w0 ``carry`` + acc,
+        P&L = W_T - payoff, statistics in the rows :meth:`pnl` writes."""
+        n = self.native
+        d = n.PnlFinishDesc()
+        for t in (acc, w0, payoff):
+            assert t.dtype == torch.float32 and t.numel() == self.n_local
+        d.acc, d.w0, d.payoff = acc.data_ptr(), w0.data_ptr(), payoff.data_ptr()
+        if pnl_out is not None:
+            assert pnl_out.dtype == torch.float32 and pnl_out.numel() == self.n_local
+        d.pnl_out = n.ptr(pnl_out)
+        d.stats = stats.data_ptr()
+        d.carry = float(carry)
+        d.n_local, d.num_wgs = self.n_local, self.pnl_wgs()
+        d.nin, d.h, d.nout, d.head = self.shape
+        assert stats.shape[0] == d.num_wgs
+        n.pnl_finish(d, self.stream)
+
     def eval(self, wts, data: DateData, stats, wts_b=None, g_base=None, blend_c=0.0, hold_c=0.0,
              v_out=None, hold_out=None, resid_out=None, pred1_out=None, snap_a=None, snap_b=None,
-             n_local: int | None = None, exercise: Exercise | None = None):
+             n_local: int | None = None, exercise: Exercise | None = None, pnl_acc=None, pnl_grow: float = 1.0,
+             pnl_carry: float = 1.0, pnl_first: bool = False):
         """k_hedge_eval over ``data`` (``n_local``: its path count when it is
         not this backend's shard, e.g. the Gram subsample; ``exercise``: the
-        date is an exercise date, ``v_out`` = max(intrinsic, continuation))."""
+        date is an exercise date, ``v_out`` = max(intrinsic, continuation)).
+
+        ``pnl_acc`` ([n] float32): fold the date's term of the self-financing
+        P&L into the eval - ``pnl_acc += pnl_carry sum_a h_a (S_a,t+1 - S_a,t
+        pnl_grow)`` with the reported holdings (``config.pnl_fold_factors``);
+        ``pnl_first``: the first accumulated date writes ``pnl_acc`` without
+        reading it.  :meth:`pnl_finish` closes the recursion after date 0."""
         _check_eval_data(self.spec, data)
         n = self.native
         d = n.EvalDesc()
@@ -667,4 +693,9 @@ class HipBackend(StateBlocks):
         _set_norm(d, data)
         if exercise is not None:
             d.ex_kind, d.ex_strike = L.EX_KINDS[exercise.kind], float(exercise.strike)
+        if pnl_acc is not None:
+            if pnl_acc.dtype != torch.float32 or pnl_acc.numel() != d.n_local:
+                raise ValueError(f"eval: pnl_acc must be float32 [{d.n_local}]")
+            d.pnl_acc = pnl_acc.data_ptr()
+            d.pnl_grow, d.pnl_carry, d.pnl_first = float(pnl_grow), float(pnl_carry), 1 if pnl_first else 0
         n.eval_(d, self.stream)

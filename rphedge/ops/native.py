@@ -62,12 +62,22 @@ class EvalDesc(C.Structure):
         ("n_local", C.c_int), ("num_wgs", C.c_int), ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int),
         ("head", C.c_int), ("fmu", C.c_float * MAXIN), ("fisd", C.c_float * MAXIN),
         ("snap_a", VP), ("snap_b", VP), ("ex_kind", C.c_int), ("ex_strike", C.c_float),
+        ("pnl_acc", VP), ("pnl_grow", C.c_float), ("pnl_carry", C.c_float), ("pnl_first", C.c_int),
+        ("pad_pnl", C.c_int),
     ]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         for f in range(MAXIN):
             self.fisd[f] = 1.0
+
+
+class PnlFinishDesc(C.Structure):
+    _fields_ = [
+        ("acc", VP), ("w0", VP), ("payoff", VP), ("pnl_out", VP), ("stats", VP),
+        ("carry", C.c_float), ("n_local", C.c_int), ("num_wgs", C.c_int),
+        ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int), ("head", C.c_int), ("pad0", C.c_int),
+    ]
 
 
 class PnlDesc(C.Structure):
@@ -145,6 +155,10 @@ def _expected_layout() -> list[int]:
         E.v_out.offset, E.hold_out.offset, E.resid_out.offset, E.pred1_out.offset, E.stats.offset,
         E.bond_t.offset, E.hold_c.offset, E.n_local.offset, E.head.offset, E.fmu.offset, E.fisd.offset,
         E.snap_a.offset, E.snap_b.offset, E.ex_kind.offset, E.ex_strike.offset,
+        E.pnl_acc.offset, E.pnl_grow.offset, E.pnl_carry.offset, E.pnl_first.offset,
+        C.sizeof(PnlFinishDesc), PnlFinishDesc.w0.offset, PnlFinishDesc.payoff.offset, PnlFinishDesc.pnl_out.offset,
+        PnlFinishDesc.stats.offset, PnlFinishDesc.carry.offset, PnlFinishDesc.n_local.offset,
+        PnlFinishDesc.num_wgs.offset, PnlFinishDesc.nin.offset, PnlFinishDesc.head.offset,
         C.sizeof(PnlDesc), PnlDesc.feat_ts.offset, PnlDesc.price.offset, PnlDesc.price_ts.offset,
         PnlDesc.snap.offset, PnlDesc.bond.offset, PnlDesc.pnl_out.offset, PnlDesc.stats.offset,
         PnlDesc.alpha.offset, PnlDesc.has_b.offset, PnlDesc.n_dates.offset, PnlDesc.head.offset,
@@ -196,6 +210,7 @@ def _bind(lib):
         "rph_train_ticket_fit": (C.c_int, [C.POINTER(TrainDesc), C.c_int, VP]),
         "rph_eval": (C.c_int, [C.POINTER(EvalDesc), VP]),
         "rph_pnl": (C.c_int, [C.POINTER(PnlDesc), VP]),
+        "rph_pnl_finish": (C.c_int, [C.POINTER(PnlFinishDesc), VP]),
         "rph_lm_shape": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 3),
         "rph_lm_pass_wps": (C.c_int, [C.c_int] * 4),
         "rph_lm_eval": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.c_int, VP]),
@@ -206,6 +221,7 @@ def _bind(lib):
                                     C.c_int, VP]),
         "rph_sobol_normal": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, C.c_longlong, C.c_int, C.c_int, VP]),
         "rph_simulate": (C.c_int, [C.POINTER(SimDesc), VP]),
+        "rph_simulate_pair": (C.c_int, [C.POINTER(SimDesc), C.POINTER(SimDesc), C.POINTER(C.c_int), VP]),
         "rph_payoff": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_float, VP, VP, VP, VP]),
         "rph_radix_hist": (C.c_int, [VP, C.c_longlong, C.c_uint32, C.c_uint32, C.c_int, C.c_int, VP, VP]),
         "rph_ipc_alloc": (C.c_int, [C.c_longlong, C.POINTER(VP), C.c_char_p]),
@@ -312,6 +328,15 @@ def simulate(desc: SimDesc, stream=None):
     _check(lib.rph_simulate(C.byref(desc), stream_handle(stream)), "rph_simulate")
 
 
+def simulate_pair(a: SimDesc, b: SimDesc, stream=None) -> bool:
+    """Scans ``a`` and ``b`` in one launch (k_sim_scan_pair) when both select
+    the same scan instantiation, else in two; returns whether it was one."""
+    lib = load(required=True)
+    merged = C.c_int(0)
+    _check(lib.rph_simulate_pair(C.byref(a), C.byref(b), C.byref(merged), stream_handle(stream)), "rph_simulate_pair")
+    return bool(merged.value)
+
+
 def train_step(desc: TrainDesc, step: int, epoch: int, stream=None):
     _check(_lib.rph_train_step(C.byref(desc), int(step), int(epoch), stream_handle(stream)), "rph_train_step")
 
@@ -402,6 +427,12 @@ def pnl(desc: PnlDesc, stream=None):
     """Self-financing hedge P&L scan over the rebalancing dates (k_hedge_pnl)."""
     load(required=True)
     _check(_lib.rph_pnl(C.byref(desc), stream_handle(stream)), "rph_pnl")
+
+
+def pnl_finish(desc: PnlFinishDesc, stream=None):
+    """Finish of the P&L folded into the evals (k_pnl_finish)."""
+    load(required=True)
+    _check(_lib.rph_pnl_finish(C.byref(desc), stream_handle(stream)), "rph_pnl_finish")
 
 
 def payoff(kind: int, s: torch.Tensor, out: torch.Tensor, strike: float, nfrac=None, wts=None, na: int = 1,

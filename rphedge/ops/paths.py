@@ -138,8 +138,13 @@ def _desc(model, n_local, offset, grid: Grid, fp64, parity, index_map=None):
 
 def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, scheme: str = "arith",
                  norm: float = 1.0, device="cuda", offset: int = 0, fp64: bool = False, seed: int = SEED_W1,
-                 stream=None, out: Paths | None = None, index_map=None, path_stat: str | None = None) -> Paths:
+                 stream=None, out: Paths | None = None, index_map=None, path_stat: str | None = None,
+                 defer: list | None = None) -> Paths:
     """Fund/stock GBM on the fine grid, stored on the coarse grid (K1+K2+K3).
+
+    ``defer`` (GPU only): append the scan's descriptor to that list instead of
+    launching it - the caller launches it, e.g. two scans in one launch with
+    ``native.simulate_pair``; the returned buffers are filled only then.
 
     ``out``: re-simulate into the buffers of an existing :class:`Paths`
     (no allocation: graph-capturable).  ``index_map``: (blk, stride) global
@@ -177,7 +182,10 @@ def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, s
         if path_stat is not None:
             d.path_stat = L.PATH_STATS[path_stat]
             d.out2, d.final2_out = A.data_ptr(), afin.data_ptr()
-        native.simulate(d, stream)
+        if defer is not None:
+            defer.append(d)
+        else:
+            native.simulate(d, stream)
     elif path_stat is None:
         s_np, f_np = _cpu_gbm(grid, n_local, s0, mu, sigma, scheme, offset, seed, index_map)
         S.copy_(torch.from_numpy((s_np / norm).astype(np.float32)))
@@ -201,8 +209,11 @@ def simulate_sv(grid: Grid, n_local: int, s0: float, mu: float, v0: float, model
                 a=0.0, b=0.0, c=0.0, kappa=0.0, theta=0.0, xi=0.0, rho=0.0, norm: float = 1.0,
                 device="cuda", offset: int = 0, fp64: bool = False, parity_nan: bool = False,
                 seed1: int = SEED_W1, seed2: int = SEED_W2, stream=None, out: Paths | None = None,
-                scheme: str = "qe", sv_tscale: float = 0.0, joint: bool | None = None, index_map=None) -> Paths:
+                scheme: str = "qe", sv_tscale: float = 0.0, joint: bool | None = None, index_map=None,
+                defer: list | None = None) -> Paths:
     """Reference CIR-on-sigma SV (RP:282-289) or Heston (K4).
+
+    ``defer``: as in :func:`simulate_gbm`.
 
     ``scheme`` (Heston): "qe" = Andersen quadratic-exponential variance step
     with the martingale-corrected log-price step (default: no visible
@@ -251,7 +262,10 @@ def simulate_sv(grid: Grid, n_local: int, s0: float, mu: float, v0: float, model
         d.sv_tscale = float(sv_tscale) if model == "sv_ref" else 0.0
         d.scheme = L.HESTON_QE if scheme == "qe" else L.HESTON_EULER
         d.out, d.out2, d.final_out = S.data_ptr(), V.data_ptr(), fin.data_ptr()
-        native.simulate(d, stream)
+        if defer is not None:
+            defer.append(d)
+        else:
+            native.simulate(d, stream)
     else:
         s_np, v_np, f_np = _cpu_sv(grid, n_local, s0, mu, v0, model, a, b, c, kappa, theta, xi, rho, offset,
                                    parity_nan, seed1, seed2, scheme=scheme,

@@ -13,8 +13,11 @@ def main():
     rows = list(c.execute("select s.kernel_name, d.start, d.end, d.grid_size_y from rocpd_kernel_dispatch d "
                           "join rocpd_info_kernel_symbol s on d.kernel_id = s.id order by d.start"))
     sims = [i for i, r in enumerate(rows) if "k_sim_scan" in r[0]]
-    start = sims[-2]  # the last replay (each replay simulates the main paths and the exploration prefix)
-    end = next(i for i in range(start, len(rows)) if "k_hedge_pnl" in rows[i][0])
+    # the last replay: it opens with one k_sim_scan_pair (the main paths and the Gram subsample in one
+    # launch), or with two k_sim_scan launches in a trace from before the merged launch
+    start = sims[-1] if "k_sim_scan_pair" in rows[sims[-1]][0] else sims[-2]
+    # ... and closes with the P&L: k_pnl_finish (folded into the evals), or the k_hedge_pnl scan
+    end = next(i for i in range(start, len(rows)) if "k_pnl_finish" in rows[i][0] or "k_hedge_pnl" in rows[i][0])
     rep = rows[start:end + 1]
     first_eval = next(i for i, r in enumerate(rep) if "k_hedge_eval" in r[0])
     agg, cnt = collections.defaultdict(float), collections.Counter()

@@ -233,7 +233,12 @@ RPH_INLINE void sim_scan_block(const SimDesc& d, const int blk) {
             if (f < 1e-300 && F < u) { break; }
           }
         } else {
-          // normal approximation (never reached by the reference configurations)
+          // N q >= 200 expected deaths in the step (or q = 1): the CDF walk
+          // would take that many iterations per thread, so D is the rounded
+          // normal approximation N q + sqrt(N q (1 - q)) z clipped to [0, N],
+          // z from the top 30 bits of the same uniform (made odd: never 0).
+          // Reached from about 10^5 members at quarterly steps, 10^6 at
+          // dt = 0.01; _cpu_mortality follows the same rule.
           const double z2n = ndtri_u30<double>((uint32_t)(u * 1073741824.0) | 1u);
           double dd = mean + sqrt(mean * (1.0 - q)) * z2n + 0.5;
           dd = dd < 0.0 ? 0.0 : (dd > (double)N ? (double)N : dd);
@@ -390,9 +395,28 @@ using namespace rph;
 
 static inline int grid_for(int n) { return (n + 255) / 256; }
 
+// The Sobol tables hold 30 direction numbers per dimension: point indices are
+// 30-bit.  Past 2^30 the two folds of sobol_point disagree (the aligned one
+// folds gray bits 30 / 31 through the zero columns, the general one stops at
+// bit 29), so a range is rejected unless [first, first + span] lies in
+// [0, 2^30).
+static constexpr long long SOBOL_INDEX_END = 1LL << 30;
+
+static int validate_sobol_range(const char* who, long long first, long long span) {
+  if (first < 0 || first >= SOBOL_INDEX_END || span < 0 || span >= SOBOL_INDEX_END - first)
+    return rph_report(who, "path range leaves the 30-bit Sobol index space [0, 2^30)");
+  return 0;
+}
+
+// The checks of rph_sobol_normal without the launch.
+extern "C" int rph_sobol_normal_check(int n, long long offset) {
+  return n > 0 ? validate_sobol_range("rph_sobol_normal", offset, (long long)n - 1) : 0;
+}
+
 extern "C" int rph_sobol_normal(void* out, int n, int d, const uint32_t* sv, const uint32_t* shift,
                                 long long offset, int fp64, int raw, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (int rc = rph_sobol_normal_check(n, offset)) return rc;
   const bool aligned = (n % 256 == 0) && (offset % 64 == 0);
   if (fp64) {
     if (aligned) hipLaunchKernelGGL((k_sobol_normal<double, true>), dim3(grid_for(n)), dim3(256), 0, s, (double*)out, n, d, sv, shift, offset, raw);
@@ -472,8 +496,22 @@ static int validate_sim(const SimDesc* d, const char* who) {
     if (d->path_stat == STAT_GEOMEAN && d->model != SIM_GBM_LOG)
       return rph_report(who, "geomean needs the log scheme (SIM_GBM_LOG)");
   }
+  if (d->n_local > 0) {
+    // the largest global index (sim_gidx of the last local path; the map is monotone), in 64 bits
+    const long long lp = (long long)d->n_local - 1;
+    long long span = lp;
+    if (d->map_blk > 0) {
+      const long long q = lp / d->map_blk;
+      if (q > 0 && d->map_stride > SOBOL_INDEX_END / q) return validate_sobol_range(who, d->path_offset, -1);
+      span = q * d->map_stride + lp % d->map_blk;
+    }
+    if (int rc = validate_sobol_range(who, d->path_offset, span)) return rc;
+  }
   return 0;
 }
+
+// The checks of rph_simulate without the launch.
+extern "C" int rph_simulate_check(const SimDesc* d) { return validate_sim(d, "rph_simulate"); }
 
 // (aligned: every wave's 64 paths are one aligned range of global indices)
 static bool sim_aligned(const SimDesc* d) {

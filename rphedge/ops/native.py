@@ -220,7 +220,9 @@ def _bind(lib):
         "rph_lm_select": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, VP, C.c_int, C.c_int, C.c_int,
                                     C.c_int, VP]),
         "rph_sobol_normal": (C.c_int, [VP, C.c_int, C.c_int, VP, VP, C.c_longlong, C.c_int, C.c_int, VP]),
+        "rph_sobol_normal_check": (C.c_int, [C.c_int, C.c_longlong]),
         "rph_simulate": (C.c_int, [C.POINTER(SimDesc), VP]),
+        "rph_simulate_check": (C.c_int, [C.POINTER(SimDesc)]),
         "rph_simulate_pair": (C.c_int, [C.POINTER(SimDesc), C.POINTER(SimDesc), C.POINTER(C.c_int), VP]),
         "rph_payoff": (C.c_int, [C.c_int, C.c_int, C.c_int, VP, VP, C.c_float, VP, VP, VP, VP]),
         "rph_radix_hist": (C.c_int, [VP, C.c_longlong, C.c_uint32, C.c_uint32, C.c_int, C.c_int, VP, VP]),
@@ -326,6 +328,18 @@ def sobol_normal(out: torch.Tensor, table, offset: int = 0, raw: bool = False, s
 def simulate(desc: SimDesc, stream=None):
     lib = load(required=True)
     _check(lib.rph_simulate(C.byref(desc), stream_handle(stream)), "rph_simulate")
+
+
+def simulate_check(desc: SimDesc):
+    """The descriptor checks of :func:`simulate` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_simulate_check(C.byref(desc)), "rph_simulate")
+
+
+def sobol_normal_check(n: int, offset: int = 0):
+    """The range check of :func:`sobol_normal` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_sobol_normal_check(int(n), int(offset)), "rph_sobol_normal")
 
 
 def simulate_pair(a: SimDesc, b: SimDesc, stream=None) -> bool:

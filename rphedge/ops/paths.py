@@ -569,7 +569,16 @@ def _cpu_basket(grid, n, s0, mu, sigma, chol, offset, seed, index_map=None):
     return out, np.exp(ly)
 
 
-def _cpu_mortality(grid, n, l0, c, eta, n0, q3, offset, seed, philox_seed, numpy_binomial, index_map=None):
+MORT_NORMAL_MEAN = 200.0   # expected deaths per step from which the kernel leaves the CDF walk (csrc/paths.hip)
+
+
+def _cpu_mortality(grid, n, l0, c, eta, n0, q3, offset, seed, philox_seed, numpy_binomial, index_map=None,
+                   branch_share: list | None = None):
+    """fp64 twin of the k_sim_scan mortality branch, the binomial draw
+    included: inversion of the Philox uniform below ``MORT_NORMAL_MEAN``
+    expected deaths in the step, the kernel's rounded normal approximation
+    from there on (and for q = 1).  ``branch_share``: a list that receives,
+    per fine step, the share of paths that took the normal approximation."""
     W2 = _normals(grid.n_fine, seed, n, offset, grid.n_fine, index_map=index_map)
     dt = grid.dt
     lam = np.full(n, float(l0))
@@ -594,12 +603,21 @@ def _cpu_mortality(grid, n, l0, c, eta, n0, q3, offset, seed, philox_seed, numpy
             f = np.exp(N * np.log1p(-np.minimum(q, 1 - 1e-16)))
             F = f.copy()
             ratio = q / np.maximum(1.0 - q, 1e-300)
-            active = (u > F) & (N > 0) & (q > 0)
+            draws = (N > 0) & (q > 0)
+            normal = draws & ((N * q >= MORT_NORMAL_MEAN) | (q >= 1.0))
+            active = (u > F) & draws & ~normal
             while active.any():
                 f = np.where(active, f * (N - D) / (D + 1) * ratio, f)
                 D = np.where(active, D + 1, D)
                 F = np.where(active, F + f, F)
                 active = active & (u > F) & (D < N)
+            if normal.any():
+                mean = N * q
+                z = ndtri_u30_f64((u * 1073741824.0).astype(np.int64) | 1)
+                dd = np.clip(mean + np.sqrt(mean * (1.0 - q)) * z + 0.5, 0.0, N)
+                D = np.where(normal, dd.astype(np.int64), D)
+            if branch_share is not None:
+                branch_share.append(float(normal.mean()))
             N = N - D
         if q3 and t < grid.n_coarse:
             LM[t] = lam

@@ -180,6 +180,84 @@ def test_launcher_rejects_bad_descriptors():
         native.train_lag_fit(d, 1, stream=0)
 
 
+def test_launchers_reject_path_ranges_past_the_sobol_table():
+    """The Sobol tables are 30-bit: rph_simulate / rph_sobol_normal report a
+    range whose largest global index is >= 2^30 before any launch, and accept
+    the ranges that end exactly on 2^30 - 1 (the dry-run entry points run the
+    launchers' checks alone, so nothing is launched here either way)."""
+    from rphedge.ops import layout as L
+    from rphedge.ops import native
+    from rphedge.ops import paths as P
+    from rphedge.ops.paths import path_indices
+
+    native.load(required=True)
+    end = 1 << 30
+    g = P.Grid(1.0, 1 / 32, 1 / 8)
+
+    def desc(n, offset, index_map=None, model=L.SIM_HESTON):
+        return P._desc(model, n, offset, g, False, False, index_map)
+
+    # the exact fits: aligned, unaligned, and a map whose last block ends on the last index
+    fits = [(512, end - 512, None), (300, end - 300, None), (1, end - 1, None), (2048, 0, None),
+            (512, end - 7 * 1024 - 64, (64, 1024)), (300, end - 5 * 1000 - 50, (50, 1000))]
+    for n, off, m in fits:
+        assert int(path_indices(n, off, m).max()) == (end - 1 if off else n - 1)
+        native.simulate_check(desc(n, off, m))
+        native.simulate_check(desc(n, off, m, model=L.SIM_BASKET))
+        if m is None:
+            native.sobol_normal_check(n, off)
+    # one past, far past, negative, and maps that leave the table only through the stride
+    past = [(512, end - 511, None), (300, end - 299, None), (1, end, None), (1, 1 << 40, None), (256, -64, None),
+            (512, end - 7 * 1024 - 63, (64, 1024)), (300, end - 5 * 1000 - 49, (50, 1000)),
+            (128, 0, (64, end)), (192, 0, (64, 1 << 62))]
+    for n, off, m in past:
+        with pytest.raises(RuntimeError, match="30-bit Sobol"):
+            native.simulate_check(desc(n, off, m))
+        with pytest.raises(RuntimeError, match="30-bit Sobol"):
+            native.simulate(desc(n, off, m, model=L.SIM_BASKET), stream=0)  # (null pointers: returns before the launch)
+        if m is None:
+            with pytest.raises(RuntimeError, match="30-bit Sobol"):
+                native.sobol_normal_check(n, off)
+    with pytest.raises(RuntimeError, match="30-bit Sobol"):
+        native.sobol_normal(torch.empty(300, 3), (torch.empty(0), torch.empty(0), 3), offset=end - 299, stream=0)
+    # the pair launcher checks both descriptors
+    with pytest.raises(RuntimeError, match="30-bit Sobol"):
+        native.simulate_pair(desc(512, 0), desc(512, end - 511), stream=0)
+
+
+def test_mortality_twin_normal_branch():
+    """_cpu_mortality follows the kernel from 200 expected deaths per step on
+    (rounded normal approximation); below it nothing changes: the n0 = 10000
+    numbers are those of the inversion-only twin."""
+    from rphedge.ops import paths as P
+
+    lam = (0.01, 0.075, 0.000597)
+    g = P.Grid(2.0, 1 / 100, 0.25)
+    share = []
+    nf, lm, nt = P._cpu_mortality(g, 515, *lam, 10000, False, 37, P.SEED_W2, 1234, False, branch_share=share)
+    assert len(share) == g.n_fine - 1 and max(share) == 0.0
+    n_t = np.rint(nt * 10000).astype(int)
+    assert n_t[:8].tolist() == [9742, 9803, 9807, 9762, 9803, 9776, 9809, 9783] and int(n_t.sum()) == 5039909
+    assert np.rint(nf[:, 3] * 10000).astype(int).tolist() == [10000, 9973, 9949, 9920, 9892, 9858, 9829, 9791, 9762]
+
+    g = P.Grid(2.0, 0.25, 0.5)
+    n0 = 100000
+    share = []
+    a = P._cpu_mortality(g, 512, *lam, n0, False, 37, P.SEED_W2, 1234, False, branch_share=share)
+    b = P._cpu_mortality(g, 512, *lam, n0, False, 37, P.SEED_W2, 1234, False)
+    assert share == [1.0] * (g.n_fine - 1)
+    for x, y in zip(a, b):
+        assert np.all(np.isfinite(x)) and np.array_equal(x, y)
+    N = a[0] * n0
+    assert np.all(np.abs(N - np.rint(N)) < 1e-6) and np.all(N >= 0) and np.all(N <= n0)
+    assert np.all(np.diff(N, axis=0) <= 0) and np.all(a[2] * n0 <= N[-1] + 1e-6)
+    # about N q = 250 deaths per quarter, sd 16: the survivors after two years
+    assert abs(float((a[2] * n0).mean()) - n0 * math.exp(-0.01 * 2.16)) < 100
+    share = []
+    P._cpu_mortality(g, 512, *lam, 80000, False, 37, P.SEED_W2, 1234, False, branch_share=share)
+    assert all(0.5 < s < 0.99 for s in share)   # N q ~ 200: both branches in every step
+
+
 # shape (nin, h, nout, head) -> net_nparams (P, R), lm_shape (P, R, NBLK) or None, lm_pass_wps:
 # the one shape table of csrc/hedge_core.h, pinned to the values before it became one table
 SHAPE_TABLE = {

@@ -24,6 +24,15 @@
 //                canonical NetWeights and the FitState bookkeeping.
 // The start point is pass 0; `passes` trial points follow.  Everything stays
 // on the device and graph-captures with the rest of the induction.
+//
+// The FINAL evaluation (pass == passes) is followed by no Marquardt step: its
+// solve only accepts / rejects and takes the output-layer (or bond-bias)
+// Newton step.  It builds no Gram tile, and in an lm_out_fix fit (out_gram:
+// k_lm_pass<BodyOG>, NarrowPairBody FINAL) it produces the four statistics,
+// the full-batch output Gram and the gradient of the output block
+// [P - NU, P) ONLY: the backward stops at the output layer, the hidden
+// entries [0, P - NU) of its packet rows and of its reduced block are exact
+// zeros, and the kernel carries neither the J tile's LDS nor the Gram code.
 #include <utility>
 
 #include "hedge_core.h"
@@ -100,7 +109,8 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
   const uint32_t kat = prefetch_kernarg_begin<(sizeof(TrainDesc) + sizeof(LmDesc) + 16 < 640 ? sizeof(TrainDesc) + sizeof(LmDesc) + 16 : 640)>();
   __shared__ __attribute__((aligned(16))) float scratch[B::SCRATCH_FLOATS];
   __shared__ __attribute__((aligned(16))) float wl[P + 4];
-  __shared__ __attribute__((aligned(16))) float jt[LM_TILE * JP];
+  // (the final-evaluation instantiation never builds a Gram tile: no J tile)
+  __shared__ __attribute__((aligned(16))) float jt[B::FINAL ? 4 : LM_TILE * JP];
   // the output-Gram image of the OG instantiation (the last passes of an lm_out_fix fit)
   __shared__ __attribute__((aligned(16))) unsigned char og_img[B::OGM ? B::OG_LDS : 16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -134,7 +144,8 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
   // the final evaluation builds no Gram tile: its solve only accepts / rejects
   // and takes the output-layer (or bias) Newton step, which read g, the
   // statistics and the output Gram - so its path schedule is the even one
-  const bool fin = pass == lm.passes;
+  // (B::FINAL, the output-Gram body: launched for that evaluation only)
+  const bool fin = B::FINAL || pass == lm.passes;
   const typename B::Sched sc =
       B::sched(d, lm.num_wgs, (gram_base > 0 || fin) ? 0 : lm.gram_wgs, lm.gram_skip, lm.leaf_blocks);
   if (path_wg) B::load(d, 0, perm, sc.b0 * 128, lane, pre);
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
     typename B::Frags fr;
     B::make_frags(wl + S::OW2, fr);
     float val[NR];
-    B::partial(d, 0, perm, wl, fr, scratch, pre, val, sc, lm.out_gram != 0, og_img,
+    B::partial(d, 0, perm, wl, fr, scratch, pre, val, sc, og_img,
                lm.slab_o + ((size_t)inst * lm.num_wgs + blockIdx.x) * 3 * 1024);
 #pragma unroll
     for (int j = 0; j < NR; ++j)
@@ -216,6 +227,8 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
   const int gtile = (int)blockIdx.x - gram_base;  // this workgroup's Gram tile
   if (fin || gtile < 0 || gtile >= lm.gram_wgs) return;
   // ---- Gram tile of 64 subsample paths (matrix cores) ------------------------
+  // (not compiled into the final-evaluation instantiation)
+  if constexpr (!B::FINAL) {
   if (wid == 0) {
     const long long slot = (long long)gtile * LM_TILE + lane;
     float x[NIN], pr[NHOLD];
@@ -322,6 +335,7 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
     for (int q = 0; q < 16; ++q) out[q * 64 + lane] = acc[q];
   }
   RPH_STAMPP(4);
+  }  // (!B::FINAL)
 #undef RPH_STAMPP
 }
 
@@ -1446,7 +1460,10 @@ static int lm_validate(const TrainDesc* d, const LmDesc* lm, int P, int R, int n
       if (!lm->dp.mbox[q]) return rph_report("rph_lm", "fused DP exchange: null peer mailbox");
   }
   if (lm->explore && lm->weights_only) return rph_report("rph_lm", "exploration fits publish nothing");
-  (void)P;
+  // the final evaluation of an output-Gram fit leaves the hidden layers'
+  // gradient [0, P - NU) at zero: the bias fallback must read the output block
+  if (lm->out_gram && lm->bias_index != -1 && (lm->bias_index < P - nu || lm->bias_index >= P))
+    return rph_report("rph_lm", "output Gram: bias_index must be -1 or an output-layer parameter");
   return 0;
 }
 

@@ -230,9 +230,12 @@ struct NarrowPairBody {
   // pass workgroups per CU: two for the 1- and 2-input free-head nets without
   // the output Gram (their body fits 256 VGPRs and 46 KB of LDS, so two waves
   // share each SIMD and fill each other's dependency stalls), else one (the
-  // output-Gram body needs 80 KB of LDS; aliased onto the Gram tile's image
-  // and capped at 256 VGPRs (4 spills) it gained 0.4 % and the bench P&L went
-  // wrong, cause not isolated: reverted, BENCHMARKS.md round 6)
+  // output-Gram body with the full backward needed 80 KB of LDS; aliased onto
+  // the Gram tile's image and capped at 256 VGPRs (4 spills) it gained 0.4 %
+  // and the bench P&L went wrong, cause not isolated: reverted, BENCHMARKS.md
+  // round 6.  The final-evaluation body below no longer has either limit, but
+  // a second workgroup per CU changes the summation tree of g_o and the
+  // output Gram: it stays at one, on 256 workgroups)
   static constexpr int WAVES_PER_SIMD = (!OG && NIN <= 2 && HEAD == HEAD_FREE && NO <= 2) ? 2 : 1;
   static constexpr int NIN_ = NIN, H_ = H, NO_ = NO, HEAD_ = HEAD;
   using S = NetShape<NIN, H, NO, HEAD>;
@@ -265,6 +268,17 @@ struct NarrowPairBody {
   static constexpr int OG_LDS = 4 * OG_ROWS * OG_PITCH;
   static constexpr bool OGM = OG && NU <= 64;
   static_assert(!OG || NU <= 64, "output-layer Gram: at most 64 output parameters");
+  // The OG instantiation runs the FINAL evaluation of a fit only (pass ==
+  // passes): its solve accepts / rejects and takes the output-layer (or bond
+  // bias) Newton step, which read the four statistics, the output Gram and
+  // the gradient of the output block [P - NU, P) - never the hidden layers'
+  // gradient.  So that body stops the backward at the output layer: no dz2,
+  // no layer-2 / layer-1 backward, no hidden accumulators (88 of the 1-8-8-2
+  // net's 106), and the packet row holds exact 0.f at [0, P - NU).  The entries
+  // that remain see the same operations in the same order as the plain body.
+  static constexpr bool FINAL = OG;
+  static_assert(!OG || LM_OUTG_TAIL == 1, "the output-Gram body is the final-evaluation body (gradient of the output block only)");
+  static_assert(P - NU == S::OW3, "the output block is [OW3, P)");
   static_assert(4 * NBO * 1024 * 4 <= OG_LDS, "the waves' output-Gram tiles reuse the image LDS");
   struct Frags {};
   struct Pre {
@@ -386,8 +400,7 @@ struct NarrowPairBody {
   // workgroup's NBO x 1024 output-Gram floats (MFMA register layout)
   RPH_INLINE static void partial(const TrainDesc& d, int step, const Perm& perm, const float* __restrict__ W,
                                  const Frags&, float* lds, Pre& pre, float (&val)[NR], const Sched& sc,
-                                 const bool og = false, unsigned char* og_lds = nullptr,
-                                 float* __restrict__ og_out = nullptr) {
+                                 unsigned char* og_lds = nullptr, float* __restrict__ og_out = nullptr) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const long long stride = sc.bstep * 128;
     const long long jend = sc.bend * 128 < d.batch ? sc.bend * 128 : d.batch;
@@ -415,17 +428,24 @@ struct NarrowPairBody {
     const bool pinball = d.loss == LOSS_PINBALL;
     const float q = d.quantile;
     Pre cur = pre;
+    // The final body must not share a SIMD with another wave: with its own 154
+    // - 160 registers (1- to 4-input nets) a second wave fits beside it, and
+    // with another process busy on the card about one evaluation in 600 of
+    // the 3-8-8-2 net then came back with the output gradient and output Gram
+    // of a few workgroups changed (never alone on the card, never the
+    // full-backward body at 256 + 4 registers; BENCHMARKS.md).  Naming the
+    // last VGPR and an AGPR sizes the allocation as that body's was: 256 + 4,
+    // one wave per SIMD whatever else runs.
+    if constexpr (FINAL) asm volatile("" ::: "v255", "a3");
     nb_f32x16 oacc[NBO];
     unsigned char* const img = og_lds + wid * OG_ROWS * OG_PITCH;
     if constexpr (OGM) {
 #pragma unroll
       for (int b = 0; b < NBO; ++b) oacc[b] = nb_f32x16{};
-      if (og) {
-        // the image's padding units [NU4, NUP) stay zero (written once)
-        constexpr int NU4 = (NU + 3) / 4 * 4;
+      // the image's padding units [NU4, NUP) stay zero (written once)
+      constexpr int NU4 = (NU + 3) / 4 * 4;
 #pragma unroll
-        for (int c0 = NU4; c0 < NUP; c0 += 4) og_put(img, lane, c0, 0.f, 0.f, 0.f, 0.f);
-      }
+      for (int c0 = NU4; c0 < NUP; c0 += 4) og_put(img, lane, c0, 0.f, 0.f, 0.f, 0.f);
     }
     for (long long j0 = sc.b0 * 128; j0 < jend; j0 += stride) {
       // opaque 16-byte-aligned weight base: every weight use is an LDS
@@ -509,11 +529,10 @@ struct NarrowPairBody {
         g[P + 2] += ape.x + ape.y;
         g[P + 3] += m.x + m.y;
       }
-      if constexpr (OGM) {
-        if (og) og_accum(img, oacc, a2, pr, m, lane);
-      }
+      if constexpr (OGM) og_accum(img, oacc, a2, pr, m, lane);
 
-      // backward
+      // backward (FINAL: the output layer's own gradient only; the hidden
+      // entries of g / gv are never touched and stay exact 0.f)
       nb_f2 dout[NO];
       if (HEAD == HEAD_COMPLEMENT) {
         dout[0] = dV * (pr[0] - pr[1]);
@@ -542,6 +561,7 @@ struct NarrowPairBody {
 #pragma unroll
           for (int j = 0; j < H; ++j) acc2(S::OW3 + j * NO + k, a2[j], dx, dy);
         }
+        if constexpr (!FINAL) {
         nb_f2 dz2[H];
 #pragma unroll
         for (int j = 0; j < H; ++j) {
@@ -579,6 +599,7 @@ struct NarrowPairBody {
 #pragma unroll
           for (int f = 0; f < NIN; ++f) acc2(S::OW1 + f * H + i, x[f], zx, zy);
         }
+        }  // (!FINAL)
       } else {
 #pragma unroll
       for (int k = 0; k < NO; ++k) g[S::OB3 + k] += dout[k].x + dout[k].y;
@@ -589,13 +610,15 @@ struct NarrowPairBody {
 #pragma unroll
         for (int k = 0; k < NO; ++k) {
           g[S::OW3 + j * NO + k] = nb_acc(g[S::OW3 + j * NO + k], a2[j], dout[k]);
-          da = nb_fma(nb_s(Wi[S::OW3 + j * NO + k]), dout[k], da);
+          if constexpr (!FINAL) da = nb_fma(nb_s(Wi[S::OW3 + j * NO + k]), dout[k], da);
         }
-        dz2[j] = nb_lrelu_bwd(a2[j], da, alpha);
-        g[S::OB2 + j] += dz2[j].x + dz2[j].y;
+        if constexpr (!FINAL) {
+          dz2[j] = nb_lrelu_bwd(a2[j], da, alpha);
+          g[S::OB2 + j] += dz2[j].x + dz2[j].y;
+        }
       }
 #pragma unroll
-      for (int i = 0; i < H; ++i) {
+      for (int i = 0; i < (FINAL ? 0 : H); ++i) {
         nb_f2 da0 = nb_s(0.f), da1 = nb_s(0.f);  // two chains (even / odd j)
 #pragma unroll
         for (int j = 0; j < H; ++j) {
@@ -623,25 +646,21 @@ struct NarrowPairBody {
 #pragma unroll
     for (int i = 0; i < PER; ++i) lds[wid * R + lane * PER + i] = g[i];
     if constexpr (OGM) {
-      if (og) {
-        // the four waves' output-Gram tiles -> one workgroup tile (fixed order)
-        float* ot = reinterpret_cast<float*>(og_lds);
-        __syncthreads();  // every wave's last fragment reads are done
+      // the four waves' output-Gram tiles -> one workgroup tile (fixed order)
+      float* ot = reinterpret_cast<float*>(og_lds);
+      __syncthreads();  // every wave's last fragment reads are done
 #pragma unroll
-        for (int b = 0; b < NBO; ++b)
+      for (int b = 0; b < NBO; ++b)
 #pragma unroll
-          for (int q = 0; q < 16; ++q) ot[(wid * NBO + b) * 1024 + q * 64 + lane] = oacc[b][q];
-      }
+        for (int q = 0; q < 16; ++q) ot[(wid * NBO + b) * 1024 + q * 64 + lane] = oacc[b][q];
     }
     __syncthreads();
     const int t = threadIdx.x;
     val[0] = (t < R) ? (lds[t] + lds[R + t]) + (lds[2 * R + t] + lds[3 * R + t]) : 0.f;
     if constexpr (OGM) {
-      if (og) {
-        const float* ot = reinterpret_cast<const float*>(og_lds);
-        for (int e = t; e < NBO * 1024; e += 256)
-          og_out[e] = (ot[e] + ot[NBO * 1024 + e]) + (ot[2 * NBO * 1024 + e] + ot[3 * NBO * 1024 + e]);
-      }
+      const float* ot = reinterpret_cast<const float*>(og_lds);
+      for (int e = t; e < NBO * 1024; e += 256)
+        og_out[e] = (ot[e] + ot[NBO * 1024 + e]) + (ot[2 * NBO * 1024 + e] + ot[3 * NBO * 1024 + e]);
     }
     __syncthreads();
   }

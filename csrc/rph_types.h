@@ -234,7 +234,11 @@ constexpr int LM_GBLK_MAX = 21 * 1024;
 // (i <= j, row-major) at LM_RED_OUTG, accumulated on the matrix cores by the
 // last LM_OUTG_TAIL evaluations of an lm_out_fix fit (NarrowPairBody OG)
 constexpr int LM_OUTG = 64 * 65 / 2;
-constexpr int LM_OUTG_TAIL = 1;  // evaluations of an lm_out_fix fit that carry it: the last one (passes)
+// evaluations of an lm_out_fix fit that carry it: the last one (passes).  That
+// evaluation's body (NarrowPairBody FINAL) relies on the value 1: it leaves
+// the hidden layers' gradient [0, P - NU) at exact zero, which no solve reads
+// after the final evaluation (static_assert in hedge_narrow.h)
+constexpr int LM_OUTG_TAIL = 1;
 constexpr int LM_RED_OUTG = LM_GBLK_MAX + LM_NPMAX + 8;
 constexpr int LM_RED = LM_RED_OUTG + LM_OUTG;
 constexpr int LM_PASS_WGS_MAX = 512;  // LM pass workgroups (two per CU for the small nets; k_lm_reduce trees)

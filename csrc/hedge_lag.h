@@ -36,7 +36,6 @@ enum LagScalar : int {
   LG_T = 0, LG_LR, LG_NAN, LG_BEST, LG_WAIT, LG_HASBEST, LG_LSUM, LG_ASUM, LG_PSUM, LG_CNT,
   LG_LASTL, LG_LASTMAE, LG_LASTMAPE, LG_SEQ /* DP sequence base, u32 bits */, LG_NSCALAR
 };
-constexpr int LAG_FLOATS = 3 * PMAX + 16;
 
 RPH_INLINE uint32_t ld_agent_u32c(const uint32_t* p) {
   return __hip_atomic_load(const_cast<uint32_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
 
 // ---------------------------------------------------------------------------
 // Self-financing hedge P&L scan (PnlDesc, rph_types.h): one thread per path
-// (PPT paths per thread), dates in lockstep per workgroup so each date's
+// (PNL_PPT paths per thread), dates in lockstep per workgroup so each date's
 // network(s) are staged once in LDS; the path inputs run one date ahead.  Wealth starts at V_0, holds the traded-
 // asset holdings of date t's network and keeps the remainder in the bank
 // account; P&L_T = W_T - liability.  Per-workgroup fp64 statistics in the
@@ -374,7 +374,6 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
 // run, a few hundred VALU flops per path and date); the corrected counterpart
 // of the reference's one-step "P&L" (Q24, Replicating_Portfolio.py:120).
 // ---------------------------------------------------------------------------
-constexpr int PNL_PPT = 4;
 
 // EX: the stopping rule of an early-exercise run (PnlDesc.ex_kind): a path is
 // frozen at its first exercise date; the workgroup still walks every date in

@@ -2,8 +2,12 @@
 //
 // Every device-resident state block is a flat float32 array so the Python side
 // (rphedge/ops/native.py) can allocate it as a torch tensor and read fields by
-// index.  The field indices below are mirrored in rphedge/ops/layout.py and
-// checked by rph_layout_check() at import time.
+// index.  The field indices and constants below are mirrored in
+// rphedge/ops/layout.py, the launch descriptors in rphedge/ops/native.py; both
+// mirrors are compared by name with the tables of rph_layout.h when the
+// library is loaded.  The descriptors have no implicit padding: every
+// alignment hole is a named pad field, so that the field lists of
+// rph_layout.h can be checked for completeness at compile time.
 #pragma once
 #include <stdint.h>
 
@@ -15,6 +19,8 @@ constexpr int MAXHOLD = 8;     // max hedging instruments (assets + bond)
 constexpr int MAXHIST = 1024;  // per-fit epoch-loss history
 constexpr int EVAL_NSTAT = 32; // doubles per workgroup in the eval stats slab
 constexpr int LAG_SLOTS = 16;  // lagged schedule: replica rows per rotating accumulator buffer
+constexpr int LAG_FLOATS = 3 * PMAX + 16;  // lagged-update state slot: w, m, v [PMAX] + 16 scalars (hedge_lag.h)
+constexpr int PNL_PPT = 4;     // paths per thread of k_hedge_pnl / k_pnl_finish
 
 enum Head : int { HEAD_FREE = 0, HEAD_COMPLEMENT = 1 };
 enum Loss : int { LOSS_MSE = 0, LOSS_PINBALL = 1 };
@@ -89,8 +95,10 @@ struct TrainDesc {
   int fused_update;              // 1: last arriver applies Adam (world_size==1)
   int num_wgs;
   int nin, h, nout, head;        // network shape (dispatch)
+  int pad_acc;
   float* acc;                    // [8][R] float-atomic accumulator (zeroed; re-armed by last arriver)
   int deterministic;             // 1: fixed-order slab reduction (bitwise reproducible)
+  int pad_stamps;
   unsigned long long* stamps;    // diagnostic phase stamps [num_wgs][8] (null in production)
   // Fused data-parallel all-reduce over xGMI peer memory (dp_world > 1):
   // mailbox of rank p = dp_mbox[p]: [DP_SLOTS][dp_world][R] floats, flags
@@ -102,8 +110,10 @@ struct TrainDesc {
   uint32_t* dp_counter;          // this rank's step sequence counter (device)
   uint32_t* dp_error;            // set on a peer timeout (host checks after the run)
   int mfma_fp32;                 // 32-unit nets: exact fp32 MFMA (32x32x2) instead of bf16 (32x32x16)
+  int pad_lag;
   float* lag;                    // lagged-update state slots [2][LAG_FLOATS] (hedge_lag.h)
   int variant;                   // kernel variant (narrow: 1 = 2 waves/SIMD, weights re-read from LDS)
+  int pad_fit_init;
   const FitState* fit_init;      // lagged schedule: fit-state template read by kernel 0, which also
                                  // writes it to `fit` (no separate template copy per fit); may be null
   float fmu[MAXIN];              // input standardisation x' = (x - fmu) * fisd, fused into the feature
@@ -134,6 +144,7 @@ struct EvalDesc {
   int nin, h, nout, head;
   float fmu[MAXIN];              // input standardisation x' = (x - fmu) * fisd (identity: 0 / 1)
   float fisd[MAXIN];
+  int pad_snap;
   // per-date weight snapshots for the saved-model format and the P&L scan:
   // workgroup 0 copies the P current weights of wa / wb into w[0] of these
   // NetWeights blocks (may be null) - no separate copy launch per date
@@ -390,6 +401,7 @@ struct LmDesc {
   // mailboxes, raise one flag each, wait for the peers' same flag and sum in
   // rank order; the pass kernel advances the exchange counter): no extra
   // launch per pass.  0: single rank, or the separate exchange kernels
+  int pad_dp;
   LmDpDesc dp;
   int dp_fused;
   // > 0: wave w of the pass grid takes the contiguous path blocks
@@ -447,7 +459,9 @@ struct SimDesc {
   int fp64;                      // recursion in double
   int parity;                    // reference quirks (SV sqrt of negative -> NaN, Q3 lambda index)
   const uint32_t* sv1; const uint32_t* shift1; int dims1;   // Sobol table A
+  int pad_sv2;
   const uint32_t* sv2; const uint32_t* shift2; int dims2;   // Sobol table B (SV / mortality)
+  int pad_s0;
   double s0[MAXIN], mu[MAXIN], sigma[MAXIN];
   double chol[MAXIN * MAXIN];
   double dt;

@@ -1,5 +1,5 @@
 // rphedge native runtime: hipGraph capture/replay, RCCL communicator over
-// xGMI, layout self-check and small device helpers.  Exposed as a C ABI and
+// xGMI, layout tables and small device helpers.  Exposed as a C ABI and
 // bound from Python with ctypes (rphedge/ops/native.py) — no torch C++ ABI
 // dependency, so the library loads into the torch process and shares its HIP
 // runtime (same SONAME libamdhip64.so.7) and RCCL (librccl.so.1).
@@ -9,7 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "rph_types.h"
+#include "rph_layout.h"
 
 using namespace rph;
 
@@ -45,57 +45,17 @@ int rph_report_shape(const char* what, int nin, int h, int nout, int head) {
 }  // namespace rph
 
 // ---------------------------------------------------------------------------
-// Layout self-check: the Python ctypes mirrors compare every offset.
+// Layout tables (rph_layout.h): the Python mirrors are compared with them by
+// name when the library is loaded.
 // ---------------------------------------------------------------------------
-#define OFF(T, f) (long long)offsetof(T, f)
-extern "C" int rph_layout(long long* out, int cap) {
-  long long v[] = {
-      (long long)sizeof(NetWeights), (long long)sizeof(OptState), (long long)sizeof(FitState),
-      OFF(NetWeights, cur), OFF(OptState, t), OFF(OptState, lr), OFF(OptState, nan_steps),
-      OFF(FitState, best_loss), OFF(FitState, stopped), OFF(FitState, epoch), OFF(FitState, last_loss),
-      OFF(FitState, restore_at_end), OFF(FitState, hist),
-      // TrainDesc
-      (long long)sizeof(TrainDesc), OFF(TrainDesc, price), OFF(TrainDesc, target), OFF(TrainDesc, wts),
-      OFF(TrainDesc, lr_sched), OFF(TrainDesc, slab), OFF(TrainDesc, counter), OFF(TrainDesc, grad_out),
-      OFF(TrainDesc, bond), OFF(TrainDesc, inv_batch), OFF(TrainDesc, loss), OFF(TrainDesc, seed),
-      OFF(TrainDesc, num_wgs), OFF(TrainDesc, head), OFF(TrainDesc, acc), OFF(TrainDesc, deterministic), OFF(TrainDesc, stamps),
-      OFF(TrainDesc, dp_world), OFF(TrainDesc, dp_mbox), OFF(TrainDesc, dp_flags), OFF(TrainDesc, dp_counter), OFF(TrainDesc, dp_error),
-      OFF(TrainDesc, fit_init), OFF(TrainDesc, fmu), OFF(TrainDesc, fisd),
-      // EvalDesc
-      (long long)sizeof(EvalDesc), OFF(EvalDesc, price_t), OFF(EvalDesc, price_t1), OFF(EvalDesc, target),
-      OFF(EvalDesc, wa), OFF(EvalDesc, g_base), OFF(EvalDesc, v_out), OFF(EvalDesc, hold_out),
-      OFF(EvalDesc, resid_out), OFF(EvalDesc, pred1_out), OFF(EvalDesc, stats), OFF(EvalDesc, bond_t),
-      OFF(EvalDesc, hold_c), OFF(EvalDesc, n_local), OFF(EvalDesc, head), OFF(EvalDesc, fmu), OFF(EvalDesc, fisd),
-      OFF(EvalDesc, snap_a), OFF(EvalDesc, snap_b), OFF(EvalDesc, ex_kind), OFF(EvalDesc, ex_strike),
-      OFF(EvalDesc, pnl_acc), OFF(EvalDesc, pnl_grow), OFF(EvalDesc, pnl_carry), OFF(EvalDesc, pnl_first),
-      // PnlFinishDesc
-      (long long)sizeof(PnlFinishDesc), OFF(PnlFinishDesc, w0), OFF(PnlFinishDesc, payoff), OFF(PnlFinishDesc, pnl_out),
-      OFF(PnlFinishDesc, stats), OFF(PnlFinishDesc, carry), OFF(PnlFinishDesc, n_local), OFF(PnlFinishDesc, num_wgs),
-      OFF(PnlFinishDesc, nin), OFF(PnlFinishDesc, head),
-      // PnlDesc
-      (long long)sizeof(PnlDesc), OFF(PnlDesc, feat_ts), OFF(PnlDesc, price), OFF(PnlDesc, price_ts),
-      OFF(PnlDesc, snap), OFF(PnlDesc, bond), OFF(PnlDesc, pnl_out), OFF(PnlDesc, stats), OFF(PnlDesc, alpha),
-      OFF(PnlDesc, has_b), OFF(PnlDesc, n_dates), OFF(PnlDesc, head),
-      OFF(PnlDesc, ex_kind), OFF(PnlDesc, ex_every), OFF(PnlDesc, ex_strike), OFF(PnlDesc, tau_out),
-      (long long)ES_EXER, (long long)ES_EXVAL, (long long)ES_CONT, (long long)ES_TAU, (long long)EVAL_NSTAT,
-      // LmDesc + LM state layout
-      (long long)sizeof(LmDesc), OFF(LmDesc, slab_b), OFF(LmDesc, slab_g), OFF(LmDesc, num_wgs),
-      OFF(LmDesc, passes), OFF(LmDesc, gram_blk), OFF(LmDesc, inv_ns), OFF(LmDesc, lam0), OFF(LmDesc, ridge), OFF(LmDesc, bias_index), OFF(LmDesc, weights_only), OFF(LmDesc, damping), OFF(LmDesc, stop_tol), OFF(LmDesc, gram_skip),
-      OFF(LmDesc, inst), OFF(LmDesc, lam_carry), OFF(LmDesc, w0), OFF(LmDesc, renorm), OFF(LmDesc, ren_isd), OFF(LmDesc, out_n), OFF(LmDesc, gfeat), OFF(LmDesc, gprice), OFF(LmDesc, gram_side), OFF(LmDesc, q_delta), OFF(LmDesc, dp), OFF(LmDesc, dp_fused), OFF(LmDesc, gtarget), OFF(LmDesc, gram_base), (long long)sizeof(LmDesc), (long long)LMS_LFIN, (long long)LMS_FAILTOT, (long long)LM_SEL_W, (long long)LM_DP_PITCH,
-      (long long)sizeof(LmDpDesc), OFF(LmDpDesc, counter), OFF(LmDpDesc, world), OFF(LmDpDesc, pitch),
-      (long long)LM_NPMAX, (long long)LM_RED, (long long)LMS_BEST, (long long)LMS_FLOATS,
-      (long long)LM_SPEC, (long long)LMS_SPEC_W, (long long)LMS_SLOTS, (long long)LM_SLOT, (long long)LSS_LBEST, (long long)LSS_STOP,
-      // SimDesc
-      (long long)sizeof(SimDesc), OFF(SimDesc, path_offset), OFF(SimDesc, sv1), OFF(SimDesc, dims1),
-      OFF(SimDesc, sv2), OFF(SimDesc, dims2), OFF(SimDesc, s0), OFF(SimDesc, chol), OFF(SimDesc, dt),
-      OFF(SimDesc, inv_norm), OFF(SimDesc, v0), OFF(SimDesc, rho), OFF(SimDesc, l0), OFF(SimDesc, n0),
-      OFF(SimDesc, seed), OFF(SimDesc, out), OFF(SimDesc, final2_out), OFF(SimDesc, sv_tscale),
-      OFF(SimDesc, scheme), OFF(SimDesc, path_stat), OFF(SimDesc, map_blk), OFF(SimDesc, map_stride),
-      (long long)LAG_SLOTS,
-  };
-  const int n = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; i < n && i < cap; ++i) out[i] = v[i];
-  return n;
+extern "C" int rph_layout_fields(const FieldRow** rows) {
+  *rows = kFieldRows;
+  return (int)(sizeof(kFieldRows) / sizeof(kFieldRows[0]));
+}
+
+extern "C" int rph_layout_consts(const ConstRow** rows) {
+  *rows = kConstRows;
+  return (int)(sizeof(kConstRows) / sizeof(kConstRows[0]));
 }
 
 // ---------------------------------------------------------------------------

@@ -14,7 +14,7 @@ from .lm_geometry import (_lm_bias_index, _lm_out_n, gram_subsample, lm_explore_
                           lm_out_nu, lm_pass_schedule, lm_shard_gram_wgs, lm_tpack_len)
 from .state import StateBlocks, _Cache, _check_eval_data, _set_norm, _steps, fit_template
 
-PNL_PPT = 4  # paths per thread of k_hedge_pnl (csrc/hedge_mlp.hip PNL_PPT)
+PNL_PPT = L.PNL_PPT  # paths per thread of k_hedge_pnl (re-exported as rphedge.engine.PNL_PPT)
 PERSISTENT_MAX_WGS = 64  # "auto" picks the persistent per-fit kernel up to this grid (1 rank)
 
 

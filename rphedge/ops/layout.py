@@ -1,9 +1,14 @@
-"""Float-index layout of the device state blocks (mirror of csrc/rph_types.h).
+"""Float-index layout of the device state blocks and the constants of csrc/rph_types.h.
 
-Checked against the native library at load time (``rph_layout``)."""
+Every upper-case int below is compared by name with the native library's table
+(csrc/rph_layout.h) at load time (``native.layout_mismatches``)."""
 PMAX = 2048
+MAXIN = 8          # max input features
+MAXHOLD = 8        # max hedging instruments (assets + bond)
 MAXHIST = 1024
 EVAL_NSTAT = 32
+PNL_PPT = 4        # paths per thread of k_hedge_pnl / k_pnl_finish
+DP_SLOTS = 4       # depth of the data-parallel mailboxes
 
 # NetWeights: float w[2][PMAX]; float cur; pad[3]
 NETW_FLOATS = 2 * PMAX + 4
@@ -65,7 +70,8 @@ LOSS_MSE, LOSS_PINBALL = 0, 1
 SIM_GBM_ARITH, SIM_GBM_LOG, SIM_SV_REF, SIM_HESTON, SIM_BASKET, SIM_MORTALITY = range(6)
 HESTON_EULER, HESTON_QE = 0, 1   # SimDesc.scheme (csrc/rph_types.h HestonScheme)
 # SimDesc.path_stat (csrc/rph_types.h PathStat): running statistic of the fine-grid GBM path
-PATH_STATS = {None: 0, "mean": 1, "geomean": 2, "max": 3, "min": 4}
+STAT_NONE, STAT_MEAN, STAT_GEOMEAN, STAT_MAX, STAT_MIN = range(5)
+PATH_STATS = {None: STAT_NONE, "mean": STAT_MEAN, "geomean": STAT_GEOMEAN, "max": STAT_MAX, "min": STAT_MIN}
 
 # Levenberg-Marquardt solver (csrc/rph_types.h LmState)
 LM_NPMAX = 192

@@ -18,6 +18,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must be loaded before librphedge.so)
 
 from . import layout as L
+from .layout import DP_SLOTS, MAXHOLD, MAXIN  # noqa: F401  (imported from here by the engine and the tests)
 
 # RPH_NATIVE_LIB=debug|asan selects the variant built by `python -m rphedge.build --debug|--asan`;
 # a path ending in .so loads that exact library (A/B of two builds, tools/ab_presets.sh)
@@ -27,8 +28,11 @@ _LIB_PATH = Path(_LIB_ENV).resolve() if _LIB_ENV.endswith(".so") else Path(__fil
 _lib = None
 _load_error: str | None = None
 
-MAXIN, MAXHOLD = 8, 8
 VP = C.c_void_p
+
+# The launch descriptors of csrc/rph_types.h, field by field, pads included
+# (the structs have no implicit padding).  load() compares every name, offset
+# and size with the native library's table (csrc/rph_layout.h).
 
 
 class TrainDesc(C.Structure):
@@ -40,10 +44,11 @@ class TrainDesc(C.Structure):
         ("loss", C.c_int), ("n_local", C.c_int), ("batch", C.c_int), ("steps_per_epoch", C.c_int),
         ("chunk_log2", C.c_int), ("shuffle", C.c_int), ("seed", C.c_uint32), ("fused_update", C.c_int),
         ("num_wgs", C.c_int), ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int), ("head", C.c_int),
-        ("acc", VP), ("deterministic", C.c_int), ("stamps", VP),
+        ("pad_acc", C.c_int), ("acc", VP), ("deterministic", C.c_int), ("pad_stamps", C.c_int), ("stamps", VP),
         ("dp_world", C.c_int), ("dp_rank", C.c_int), ("dp_mbox", VP * 8), ("dp_flags", VP * 8),
-        ("dp_counter", VP), ("dp_error", VP), ("mfma_fp32", C.c_int), ("lag", VP), ("variant", C.c_int),
-        ("fit_init", VP), ("fmu", C.c_float * MAXIN), ("fisd", C.c_float * MAXIN),
+        ("dp_counter", VP), ("dp_error", VP), ("mfma_fp32", C.c_int), ("pad_lag", C.c_int), ("lag", VP),
+        ("variant", C.c_int), ("pad_fit_init", C.c_int), ("fit_init", VP),
+        ("fmu", C.c_float * MAXIN), ("fisd", C.c_float * MAXIN),
     ]
 
     def __init__(self, *a, **kw):
@@ -61,7 +66,7 @@ class EvalDesc(C.Structure):
         ("hold_c", C.c_float),
         ("n_local", C.c_int), ("num_wgs", C.c_int), ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int),
         ("head", C.c_int), ("fmu", C.c_float * MAXIN), ("fisd", C.c_float * MAXIN),
-        ("snap_a", VP), ("snap_b", VP), ("ex_kind", C.c_int), ("ex_strike", C.c_float),
+        ("pad_snap", C.c_int), ("snap_a", VP), ("snap_b", VP), ("ex_kind", C.c_int), ("ex_strike", C.c_float),
         ("pnl_acc", VP), ("pnl_grow", C.c_float), ("pnl_carry", C.c_float), ("pnl_first", C.c_int),
         ("pad_pnl", C.c_int),
     ]
@@ -112,7 +117,7 @@ class LmDesc(C.Structure):
         ("out_n", C.c_int), ("out_mu", C.c_float), ("out_gram", C.c_int), ("out_tr", C.c_float),
         ("slab_o", VP),
         ("gfeat", VP * MAXIN), ("gprice", VP * MAXIN), ("gram_side", C.c_int), ("q_delta", C.c_float), ("q_kappa", C.c_float),
-        ("dp", LmDpDesc), ("dp_fused", C.c_int), ("leaf_blocks", C.c_int), ("gtarget", VP),
+        ("pad_dp", C.c_int), ("dp", LmDpDesc), ("dp_fused", C.c_int), ("leaf_blocks", C.c_int), ("gtarget", VP),
         ("gram_base", C.c_int), ("pad4", C.c_int),
     ]
 
@@ -126,8 +131,8 @@ class SimDesc(C.Structure):
         ("model", C.c_int), ("n_local", C.c_int), ("path_offset", C.c_longlong),
         ("n_fine", C.c_int), ("reduction", C.c_int), ("n_coarse", C.c_int), ("na", C.c_int),
         ("fp64", C.c_int), ("parity", C.c_int),
-        ("sv1", VP), ("shift1", VP), ("dims1", C.c_int),
-        ("sv2", VP), ("shift2", VP), ("dims2", C.c_int),
+        ("sv1", VP), ("shift1", VP), ("dims1", C.c_int), ("pad_sv2", C.c_int),
+        ("sv2", VP), ("shift2", VP), ("dims2", C.c_int), ("pad_s0", C.c_int),
         ("s0", C.c_double * MAXIN), ("mu", C.c_double * MAXIN), ("sigma", C.c_double * MAXIN),
         ("chol", C.c_double * (MAXIN * MAXIN)), ("dt", C.c_double), ("inv_norm", C.c_double * MAXIN),
         ("v0", C.c_double), ("a", C.c_double), ("b", C.c_double), ("c", C.c_double),
@@ -139,53 +144,58 @@ class SimDesc(C.Structure):
     ]
 
 
-def _expected_layout() -> list[int]:
-    f = 4
-    T, E, S = TrainDesc, EvalDesc, SimDesc
-    return [
-        L.NETW_FLOATS * f, L.OPT_FLOATS * f, L.FIT_FLOATS * f,
-        L.W_CUR * f, L.O_T * f, L.O_LR * f, L.O_NAN * f,
-        L.F_BEST * f, L.F_STOPPED * f, L.F_EPOCH * f, L.F_LAST_LOSS * f, L.F_RESTORE_END * f, L.F_HIST * f,
-        C.sizeof(T), T.price.offset, T.target.offset, T.wts.offset, T.lr_sched.offset, T.slab.offset,
-        T.counter.offset, T.grad_out.offset, T.bond.offset, T.inv_batch.offset, T.loss.offset, T.seed.offset,
-        T.num_wgs.offset, T.head.offset, T.acc.offset, T.deterministic.offset, T.stamps.offset,
-        T.dp_world.offset, T.dp_mbox.offset, T.dp_flags.offset, T.dp_counter.offset, T.dp_error.offset,
-        T.fit_init.offset, T.fmu.offset, T.fisd.offset,
-        C.sizeof(E), E.price_t.offset, E.price_t1.offset, E.target.offset, E.wa.offset, E.g_base.offset,
-        E.v_out.offset, E.hold_out.offset, E.resid_out.offset, E.pred1_out.offset, E.stats.offset,
-        E.bond_t.offset, E.hold_c.offset, E.n_local.offset, E.head.offset, E.fmu.offset, E.fisd.offset,
-        E.snap_a.offset, E.snap_b.offset, E.ex_kind.offset, E.ex_strike.offset,
-        E.pnl_acc.offset, E.pnl_grow.offset, E.pnl_carry.offset, E.pnl_first.offset,
-        C.sizeof(PnlFinishDesc), PnlFinishDesc.w0.offset, PnlFinishDesc.payoff.offset, PnlFinishDesc.pnl_out.offset,
-        PnlFinishDesc.stats.offset, PnlFinishDesc.carry.offset, PnlFinishDesc.n_local.offset,
-        PnlFinishDesc.num_wgs.offset, PnlFinishDesc.nin.offset, PnlFinishDesc.head.offset,
-        C.sizeof(PnlDesc), PnlDesc.feat_ts.offset, PnlDesc.price.offset, PnlDesc.price_ts.offset,
-        PnlDesc.snap.offset, PnlDesc.bond.offset, PnlDesc.pnl_out.offset, PnlDesc.stats.offset,
-        PnlDesc.alpha.offset, PnlDesc.has_b.offset, PnlDesc.n_dates.offset, PnlDesc.head.offset,
-        PnlDesc.ex_kind.offset, PnlDesc.ex_every.offset, PnlDesc.ex_strike.offset, PnlDesc.tau_out.offset,
-        L.ES_EXER, L.ES_EXVAL, L.ES_CONT, L.ES_TAU, L.EVAL_NSTAT,
-        C.sizeof(LmDesc), LmDesc.slab_b.offset, LmDesc.slab_g.offset, LmDesc.num_wgs.offset,
-        LmDesc.passes.offset, LmDesc.gram_blk.offset, LmDesc.inv_ns.offset, LmDesc.lam0.offset,
-        LmDesc.ridge.offset, LmDesc.bias_index.offset, LmDesc.weights_only.offset, LmDesc.damping.offset, LmDesc.stop_tol.offset, LmDesc.gram_skip.offset,
-        LmDesc.inst.offset, LmDesc.lam_carry.offset, LmDesc.w0.offset, LmDesc.renorm.offset,
-        LmDesc.ren_isd.offset, LmDesc.out_n.offset, LmDesc.gfeat.offset, LmDesc.gprice.offset,
-        LmDesc.gram_side.offset, LmDesc.q_delta.offset, LmDesc.dp.offset, LmDesc.dp_fused.offset, LmDesc.gtarget.offset, LmDesc.gram_base.offset, C.sizeof(LmDesc),
-        L.LMS_LFIN, L.LMS_FAILTOT, L.LM_SEL_W, L.LM_DP_PITCH,
-        C.sizeof(LmDpDesc), LmDpDesc.counter.offset, LmDpDesc.world.offset, LmDpDesc.pitch.offset,
-        L.LM_NPMAX, L.LM_RED, L.LMS_BEST, L.LMS_FLOATS,
-        L.LM_SPEC, L.LMS_SPEC_W, L.LMS_SLOTS, L.LM_SLOT, L.LSS_LBEST, L.LSS_STOP,
-        C.sizeof(S), S.path_offset.offset, S.sv1.offset, S.dims1.offset, S.sv2.offset, S.dims2.offset,
-        S.s0.offset, S.chol.offset, S.dt.offset, S.inv_norm.offset, S.v0.offset, S.rho.offset, S.l0.offset,
-        S.n0.offset, S.seed.offset, S.out.offset, S.final2_out.offset, S.sv_tscale.offset, S.scheme.offset, S.path_stat.offset,
-        S.map_blk.offset, S.map_stride.offset,
-        L.LAG_SLOTS,
-    ]
+DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, SimDesc)
+
+# upper-case ints of layout.py that the native table does not hold (Python only)
+PYTHON_ONLY: tuple[str, ...] = ()
+
+
+class _FieldRow(C.Structure):  # csrc/rph_layout.h FieldRow
+    _fields_ = [("strct", C.c_char_p), ("field", C.c_char_p), ("offset", C.c_uint), ("size", C.c_uint)]
+
+
+class _ConstRow(C.Structure):  # csrc/rph_layout.h ConstRow
+    _fields_ = [("name", C.c_char_p), ("value", C.c_longlong)]
+
+
+def native_layout(lib) -> tuple[list[tuple[str, str, int, int]], list[tuple[str, int]]]:
+    """The library's tables: (struct, field, offset, size) of every descriptor
+    field in declaration order, and (name, value) of every constant."""
+    fr, cr = C.POINTER(_FieldRow)(), C.POINTER(_ConstRow)()
+    nf, nc = lib.rph_layout_fields(C.byref(fr)), lib.rph_layout_consts(C.byref(cr))
+    return ([(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]],
+            [(r.name.decode(), r.value) for r in cr[:nc]])
+
+
+def layout_mismatches(fields, consts, classes=DESCRIPTORS, layout=L) -> list[str]:
+    """Every difference between the native tables (:func:`native_layout`) and
+    the Python mirrors: the ctypes ``classes`` field by field (offset and size
+    by name, which fixes the order too) and their sizes, and the constants of
+    ``layout``, both ways."""
+    bad = []
+    for cls in classes:
+        s = cls.__name__
+        nat = {f: (o, z) for t, f, o, z in fields if t == s}
+        py = {f[0]: (getattr(cls, f[0]).offset, getattr(cls, f[0]).size) for f in cls._fields_}
+        say = lambda v, side: f"{side} offset {v[0]} size {v[1]}" if v else f"not in {side}"  # noqa: E731
+        bad += [f"{s}.{f}: {say(nat.get(f), 'native')}, {say(py.get(f), 'ctypes')}"
+                for f in dict(nat, **py) if nat.get(f) != py.get(f)]
+        size = max((o + z for o, z in nat.values()), default=0)  # (the native list is gapless: static_assert)
+        if size != C.sizeof(cls):
+            bad.append(f"{s}: native size {size}, ctypes size {C.sizeof(cls)}")
+    nat = dict(consts)
+    py = {k: v for k, v in vars(layout).items() if k.isupper() and type(v) is int}
+    bad += [f"layout.{k}: native {v}, python {py.get(k, 'has none')}" for k, v in nat.items() if py.get(k) != v]
+    bad += [f"layout.{k}: python {v}, not in the native table" for k, v in py.items()
+            if k not in nat and k not in PYTHON_ONLY]
+    return bad
 
 
 def _bind(lib):
     sig = {
         "rph_last_error": (C.c_char_p, []),
-        "rph_layout": (C.c_int, [C.POINTER(C.c_longlong), C.c_int]),
+        "rph_layout_fields": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_layout_consts": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
         "rph_device_info": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong),
                                       C.c_char_p, C.c_int]),
         "rph_memset_async": (C.c_int, [VP, C.c_int, C.c_longlong, VP]),
@@ -257,13 +267,9 @@ def load(required: bool | None = None):
             _build.build(debug=v == "debug", asan=v == "asan")
         lib = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         _bind(lib)
-        cap = 256
-        buf = (C.c_longlong * cap)()
-        n = lib.rph_layout(buf, cap)
-        got = list(buf[:n])
-        exp = _expected_layout()
-        if got != exp:
-            raise RuntimeError(f"native/ctypes layout mismatch:\n native={got}\n python={exp}")
+        bad = layout_mismatches(*native_layout(lib))
+        if bad:
+            raise RuntimeError("native/Python layout mismatch:\n  " + "\n  ".join(bad))
         _lib = lib
         return lib
     except Exception as e:  # pragma: no cover - exercised on broken installs only
@@ -541,9 +547,6 @@ class NcclComm:
         if self.comm is not None:
             _lib.rph_nccl_destroy(self.comm)
             self.comm = None
-
-
-DP_SLOTS = 4
 
 
 class IpcMailbox:

@@ -1,4 +1,5 @@
 """CPU tests: host twins of the device math, config/API plumbing, CPU engine."""
+import ctypes
 import math
 
 import numpy as np
@@ -74,6 +75,107 @@ def test_native_layout_loads_without_gpu():
     assert lib is not None
     assert native.net_nparams(3, 8, 2, 0) == (122, 128)
     assert native.net_nparams(1, 8, 1, 1) == (97, 128)
+
+
+@pytest.fixture(scope="module")
+def native_tables():
+    from rphedge.ops import native
+
+    return native.native_layout(native.load(required=False))
+
+
+def _mirror(cls, edit):
+    """A copy of the ctypes mirror ``cls`` with ``edit`` applied to its field list."""
+    fields = list(cls._fields_)
+    edit(fields, [f[0] for f in fields].index)
+    return type(cls.__name__, (ctypes.Structure,), {"_fields_": fields})
+
+
+def _swap(a, b):
+    def edit(fields, at):
+        fields[at(a)], fields[at(b)] = fields[at(b)], fields[at(a)]
+    return edit
+
+
+def _drop(name):
+    return lambda fields, at: fields.pop(at(name))
+
+
+def _retype(name, ctype):
+    def edit(fields, at):
+        fields[at(name)] = (name, ctype)
+    return edit
+
+
+def test_native_field_table_is_complete_and_matches(native_tables):
+    from rphedge.ops import native
+
+    fields, consts = native_tables
+    assert len(fields) == sum(len(c._fields_) for c in native.DESCRIPTORS) == 215 + 8
+    assert native.layout_mismatches(fields, consts) == []
+    assert [ctypes.sizeof(c) for c in native.DESCRIPTORS] == [536, 480, 72, 384, 96, 488, 1032]
+
+
+MUTATIONS = {
+    "swap n_local/batch": ("TrainDesc", _swap("n_local", "batch"), ["n_local", "batch"]),
+    "swap out2/out3": ("SimDesc", _swap("out2", "out3"), ["out2", "out3"]),
+    "swap world/rank": ("LmDpDesc", _swap("world", "rank"), ["world", "rank"]),
+    "drop lam_up": ("LmDesc", _drop("lam_up"), ["lam_up"]),
+    "float to double": ("EvalDesc", _retype("hold_c", ctypes.c_double), ["hold_c"]),
+    "drop pad_acc": ("TrainDesc", _drop("pad_acc"), ["pad_acc"]),   # (no offset moves: the hole comes back)
+    "drop pad4": ("LmDesc", _drop("pad4"), ["pad4"]),               # (nor does the size: tail alignment)
+}
+
+
+@pytest.mark.parametrize("case", MUTATIONS)
+def test_layout_comparison_names_a_wrong_mirror(native_tables, case):
+    from rphedge.ops import native
+
+    struct, edit, named = MUTATIONS[case]
+    fields, consts = native_tables
+    classes = tuple(_mirror(c, edit) if c.__name__ == struct else c for c in native.DESCRIPTORS)
+    bad = native.layout_mismatches(fields, consts, classes=classes)
+    for f in named:
+        assert any(line.startswith(f"{struct}.{f}: ") for line in bad), (f, bad)
+    assert all(line.startswith(struct) for line in bad), bad   # (no other struct is blamed)
+    assert native.layout_mismatches(fields, consts) == []      # (the module's own mirrors are untouched)
+
+
+def test_layout_comparison_names_a_wrong_constant(native_tables):
+    import types
+
+    from rphedge.ops import layout, native
+
+    fields, consts = native_tables
+
+    def bad(**edit):
+        ns = dict(vars(layout))
+        for k, v in edit.items():
+            ns.pop(k) if v is None else ns.__setitem__(k, v)
+        return native.layout_mismatches(fields, consts, layout=types.SimpleNamespace(**ns))
+
+    assert bad() == []
+    out = bad(LM_OUTG_TAIL=2)
+    assert len(out) == 1 and out[0].startswith("layout.LM_OUTG_TAIL:") and "native 1" in out[0] and "python 2" in out[0]
+    out = bad(ES_TAU=None)
+    assert len(out) == 1 and out[0].startswith("layout.ES_TAU:") and "native 29" in out[0]
+    out = bad(NEW_KNOB=7)
+    assert len(out) == 1 and out[0].startswith("layout.NEW_KNOB:") and "not in the native table" in out[0]
+
+
+def test_native_constants_resolve_in_layout(native_tables):
+    from rphedge.ops import layout, native
+
+    names = [n for n, _ in native_tables[1]]
+    assert len(names) == len(set(names))
+    assert [n for n in names if not isinstance(getattr(layout, n, None), int)] == []
+    assert [n for n in native.PYTHON_ONLY if n in names] == []
+    assert all(isinstance(getattr(layout, n), int) for n in native.PYTHON_ONLY)
+    # the copies that used to live elsewhere are the layout module's
+    import rphedge.engine as E
+
+    assert (native.MAXIN, native.MAXHOLD, native.DP_SLOTS) == (layout.MAXIN, layout.MAXHOLD, layout.DP_SLOTS)
+    assert E.MAXIN == layout.MAXIN == 8 and E.PNL_PPT == layout.PNL_PPT == 4
 
 
 def test_param_counts_match_reference():

@@ -16,23 +16,9 @@
 #include "rph_common.h"
 #include "rph_types.h"
 
-namespace rph {
-int rph_report(const char* what, const char* msg);  // runtime.cpp
-}
+#include "sim_step.h"  // the per-step scan code (shared with hedge_oos.hip), ndtri_u30, sim_gidx
 
 namespace rph {
-
-template <typename Real>
-RPH_INLINE Real ndtri_u30(uint32_t x);
-template <>
-RPH_INLINE float ndtri_u30<float>(uint32_t x) {
-  x = x == 0u ? 1u : x;  // fp32 path: keep samples finite (x==0 has probability 2^-30)
-  return ndtri_u30_f32(x);
-}
-template <>
-RPH_INLINE double ndtri_u30<double>(uint32_t x) {
-  return ndtri_u30_f64(x);
-}
 
 // Standalone K1+K2: out[i*d + j] (path-major like scipy) of N(0,1) draws.
 template <typename Real, bool ALIGNED>
@@ -52,13 +38,6 @@ __global__ __launch_bounds__(256) void k_sobol_normal(Real* __restrict__ out, in
   }
 }
 
-// global (Sobol / Philox) index of local path p (SimDesc.map_blk: the LM Gram
-// subsample, a few aligned blocks of the global range, simulated on every rank)
-RPH_INLINE long long sim_gidx(const SimDesc& d, int p) {
-  return d.map_blk > 0 ? d.path_offset + ((long long)p / d.map_blk) * d.map_stride + (long long)p % d.map_blk
-                       : d.path_offset + p;
-}
-
 // ---------------------------------------------------------------------------
 // Single-asset / SV / Heston / mortality scans.
 // ---------------------------------------------------------------------------
@@ -76,130 +55,49 @@ RPH_INLINE void sim_scan_block(const SimDesc& d, const int blk) {
   const uint32_t g = gray_code((uint64_t)gp);
   const Real dt = (Real)d.dt;
   const Real sdt = sqrt(dt);
-  const Real mu = (Real)d.mu[0], sig = (Real)d.sigma[0];
   const float inv0 = (float)d.inv_norm[0];
   const size_t n = (size_t)d.n_local;
 
   if (MODEL == SIM_GBM_ARITH || MODEL == SIM_GBM_LOG) {
-    Real y = (MODEL == SIM_GBM_LOG) ? log((Real)d.s0[0]) : (Real)d.s0[0];
-    const Real drift = (MODEL == SIM_GBM_LOG) ? (mu - (Real)0.5 * sig * sig) * dt : mu * dt;
-    const Real vol = sig * sdt;
+    GbmScan<Real, MODEL, STAT> gs;  // (sim_step.h)
+    gs.init(d);
     d.out[p] = (float)d.s0[0] * inv0;
-    // running sum of S (mean) / of log S (geomean), or running extreme from S_0
-    Real acc = (STAT == STAT_MEAN || STAT == STAT_GEOMEAN) ? (Real)0 : (Real)d.s0[0];
-    Real stat = (Real)d.s0[0];  // the statistic at the current fine point (S_0 at j = 0)
-    Real sf = (Real)d.s0[0];    // S at the current fine point (STAT: mean / max / min)
     if (STAT != STAT_NONE) d.out2[p] = (float)d.s0[0] * inv0;
     for (int t = 1; t < d.n_fine; ++t) {
       const Real z = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
-      if (MODEL == SIM_GBM_LOG) y += drift + vol * z;
-      else y = y + y * (drift + vol * z);
-      if (STAT == STAT_GEOMEAN) {
-        acc += y;  // (log scheme only: the sum of log S, no exp per step)
-      } else if (STAT != STAT_NONE) {
-        sf = (MODEL == SIM_GBM_LOG) ? exp(y) : y;
-        if (STAT == STAT_MEAN) acc += sf;
-        else if (STAT == STAT_MAX) acc = sf > acc ? sf : acc;
-        else acc = sf < acc ? sf : acc;
-      }
-      if (t % d.reduction == 0 || (STAT != STAT_NONE && t == d.n_fine - 1)) {
-        if (STAT == STAT_MEAN) stat = acc / (Real)t;
-        else if (STAT == STAT_GEOMEAN) stat = exp(acc / (Real)t);
-        else if (STAT != STAT_NONE) stat = acc;
-      }
+      gs.step(z);
+      if (t % d.reduction == 0 || (STAT != STAT_NONE && t == d.n_fine - 1)) gs.refresh(t);
       if (t % d.reduction == 0) {
         const int c = t / d.reduction;
-        const Real s = (STAT != STAT_NONE && STAT != STAT_GEOMEAN) ? sf : ((MODEL == SIM_GBM_LOG) ? exp(y) : y);
+        const Real s = gs.price();
         if (c < d.n_coarse) {
           d.out[(size_t)c * n + p] = (float)s * inv0;
-          if (STAT != STAT_NONE) d.out2[(size_t)c * n + p] = (float)stat * inv0;
+          if (STAT != STAT_NONE) d.out2[(size_t)c * n + p] = (float)gs.stat * inv0;
         }
       }
     }
-    const Real s = (STAT != STAT_NONE && STAT != STAT_GEOMEAN) ? sf : ((MODEL == SIM_GBM_LOG) ? exp(y) : y);
+    const Real s = gs.price();
     if (d.final_out) d.final_out[p] = (float)s * inv0;
-    if (STAT != STAT_NONE && d.final2_out) d.final2_out[p] = (float)stat * inv0;
+    if (STAT != STAT_NONE && d.final2_out) d.final2_out[p] = (float)gs.stat * inv0;
   } else if (MODEL == SIM_SV_REF || MODEL == SIM_HESTON) {
     // table 1 -> price shocks (W1, seed 1235), table 2 -> variance shocks (W_SV)
-    Real ly = log((Real)d.s0[0]);
-    Real v = (Real)d.v0;
+    SvScan<Real, MODEL> ss;  // (sim_step.h)
+    ss.init(d);
     d.out[p] = (float)d.s0[0] * inv0;
-    if (d.out2) d.out2[p] = (float)v;
-    const Real rho = (Real)d.rho, rhoc = sqrt((Real)1 - rho * rho);
-    // Andersen (2008) QE constants (uniform over the launch): variance moments
-    // m = theta + (v - theta) e^{-kappa dt}, s^2 = v*qc1 + qc2; log-price
-    // central discretisation gamma1 = gamma2 = 1/2 (K1..K4) with the
-    // martingale-corrected K0* (E[S_{t+dt}] = S_t e^{mu dt} exactly)
-    const Real kap = (Real)d.kappa, th = (Real)d.theta, xi = (Real)d.xi;
-    const Real ekd = exp(-kap * dt);
-    const Real qc1 = xi * xi * ekd * ((Real)1 - ekd) / kap;
-    const Real qc2 = th * xi * xi * ((Real)1 - ekd) * ((Real)1 - ekd) / ((Real)2 * kap);
-    const Real qK1 = (Real)0.5 * dt * (kap * rho / xi - (Real)0.5) - rho / xi;
-    const Real qK2 = (Real)0.5 * dt * (kap * rho / xi - (Real)0.5) + rho / xi;
-    const Real qK3 = (Real)0.5 * dt * ((Real)1 - rho * rho);
-    const Real qA = qK2 + (Real)0.5 * qK3;
-    const Real qK0u = -rho * kap * th * dt / xi;  // uncorrected K0 (when the correction does not exist)
-    const bool qe = MODEL == SIM_HESTON && d.scheme == HESTON_QE;
-    const Real tau = (Real)d.sv_tscale * dt;  // SV_REF corrected: calibration-day time step
+    if (d.out2) d.out2[p] = (float)ss.v;
     for (int t = 1; t < d.n_fine; ++t) {
       const Real z1 = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
       const uint32_t x2 = sobol_point<ALIGNED>(d.sv2 + (size_t)t * 32, d.shift2[t], g);
-      if (MODEL == SIM_SV_REF) {
-        const Real z2 = ndtri_u30<Real>(x2);
-        if (d.sv_tscale > 0.0) {
-          // corrected CIR-on-sigma: rates in calibration-day units, full
-          // truncation, price shock with the start-of-step volatility
-          const Real vp = v > (Real)0 ? v : (Real)0;
-          ly += (mu - (Real)0.5 * vp * vp) * dt + vp * sdt * z1;
-          v = v + (Real)d.a * ((Real)d.b - vp) * tau + (Real)d.c * sqrt(vp * tau) * z2;
-        } else {
-          // RP:285  vt = vt + a(b - vt) + c sqrt(vt dt) W_SV   (no dt on the drift: Q5)
-          const Real arg = v * dt;
-          const Real sq = d.parity ? sqrt(arg) : sqrt(arg > (Real)0 ? arg : (Real)0);  // parity: NaN like numpy
-          v = v + (Real)d.a * ((Real)d.b - v) + (Real)d.c * sq * z2;
-          // RP:287  logY += (mu - vt^2/2) dt + vt sqrt(dt) W1   (vt used as a volatility)
-          ly += (mu - (Real)0.5 * v * v) * dt + v * sdt * z1;
-        }
-      } else if (qe) {
-        const Real m = th + (v - th) * ekd;
-        const Real s2 = v * qc1 + qc2;
-        const Real psi = s2 / (m * m);
-        Real vn, k0;
-        if (psi <= (Real)1.5) {  // quadratic branch: v' = a (b + Z)^2
-          const Real z2 = ndtri_u30<Real>(x2);
-          const Real ip = (Real)2 / psi;
-          const Real b2 = ip - (Real)1 + sqrt(ip) * sqrt(ip - (Real)1);
-          const Real qa = m / ((Real)1 + b2);
-          const Real bz = sqrt(b2) + z2;
-          vn = qa * bz * bz;
-          const Real den = (Real)1 - (Real)2 * qA * qa;
-          k0 = den > (Real)0 ? -qA * b2 * qa / den + (Real)0.5 * log(den) - (qK1 + (Real)0.5 * qK3) * v : qK0u;
-        } else {  // exponential branch: point mass p at 0, exponential tail (inverse CDF of the uniform)
-          const Real p = (psi - (Real)1) / (psi + (Real)1);
-          const Real beta = ((Real)1 - p) / m;
-          const Real u = (Real)x2 * (Real)9.313225746154785e-10;
-          vn = u <= p ? (Real)0 : log(((Real)1 - p) / ((Real)1 - u)) / beta;
-          k0 = beta > qA ? -log(p + beta * ((Real)1 - p) / (beta - qA)) - (qK1 + (Real)0.5 * qK3) * v : qK0u;
-        }
-        const Real var = qK3 * (v + vn);
-        ly += mu * dt + k0 + qK1 * v + qK2 * vn + sqrt(var > (Real)0 ? var : (Real)0) * z1;
-        v = vn;
-      } else {
-        const Real z2 = ndtri_u30<Real>(x2);
-        const Real vp = v > (Real)0 ? v : (Real)0;
-        const Real sv = sqrt(vp * dt);
-        ly += (mu - (Real)0.5 * vp) * dt + sv * (rho * z2 + rhoc * z1);
-        v = v + (Real)d.kappa * ((Real)d.theta - vp) * dt + (Real)d.xi * sv * z2;
-      }
+      ss.step(d, z1, x2);
       if (t % d.reduction == 0) {
         const int c = t / d.reduction;
         if (c < d.n_coarse) {
-          d.out[(size_t)c * n + p] = (float)exp(ly) * inv0;
-          if (d.out2) d.out2[(size_t)c * n + p] = (float)v;
+          d.out[(size_t)c * n + p] = (float)ss.price() * inv0;
+          if (d.out2) d.out2[(size_t)c * n + p] = (float)ss.v;
         }
       }
     }
-    if (d.final_out) d.final_out[p] = (float)exp(ly) * inv0;
+    if (d.final_out) d.final_out[p] = (float)ss.price() * inv0;
   } else if (MODEL == SIM_MORTALITY) {
     // RP:73-76 lambda Euler (Sobol seed 1234); RP:78-84 N_t ~ Binom(N_{t-1}, exp(-lambda_t dt)).
     Real lam = (Real)d.l0;
@@ -394,19 +292,6 @@ __global__ __launch_bounds__(256) void k_radix_hist(const float* __restrict__ x,
 using namespace rph;
 
 static inline int grid_for(int n) { return (n + 255) / 256; }
-
-// The Sobol tables hold 30 direction numbers per dimension: point indices are
-// 30-bit.  Past 2^30 the two folds of sobol_point disagree (the aligned one
-// folds gray bits 30 / 31 through the zero columns, the general one stops at
-// bit 29), so a range is rejected unless [first, first + span] lies in
-// [0, 2^30).
-static constexpr long long SOBOL_INDEX_END = 1LL << 30;
-
-static int validate_sobol_range(const char* who, long long first, long long span) {
-  if (first < 0 || first >= SOBOL_INDEX_END || span < 0 || span >= SOBOL_INDEX_END - first)
-    return rph_report(who, "path range leaves the 30-bit Sobol index space [0, 2^30)");
-  return 0;
-}
 
 // The checks of rph_sobol_normal without the launch.
 extern "C" int rph_sobol_normal_check(int n, long long offset) {

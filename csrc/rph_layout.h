@@ -52,8 +52,16 @@ namespace rph {
   X(T, theta) X(T, xi) X(T, rho) X(T, l0) X(T, lc) X(T, eta) X(T, n0) X(T, seed) X(T, out) X(T, out2) X(T, out3)    \
   X(T, final_out) X(T, final2_out) X(T, sv_tscale) X(T, scheme) X(T, path_stat) X(T, map_blk) X(T, map_stride)
 
+#define RPH_FIELDS_OosDesc(X, T)                                                                                    \
+  X(T, sim) X(T, snap) X(T, fmu) X(T, fisd) X(T, bond) X(T, pnl_out) X(T, payoff_out) X(T, stats) X(T, alpha)       \
+  X(T, hold_c) X(T, wealth0) X(T, strike) X(T, has_b) X(T, payoff_kind) X(T, n_dates) X(T, num_wgs) X(T, nin)       \
+  X(T, h) X(T, nout) X(T, head)
+
 #define RPH_DESCRIPTORS(X) \
   X(TrainDesc) X(EvalDesc) X(PnlFinishDesc) X(PnlDesc) X(LmDpDesc) X(LmDesc) X(SimDesc)
+// Descriptors of later kernels, in a table of their own (rph_layout_fields_ext;
+// native.py DESCRIPTORS_EXT): checked by name at load exactly like the first.
+#define RPH_DESCRIPTORS_EXT(X) X(OosDesc)
 
 struct FieldRow {
   const char* strct;
@@ -64,6 +72,7 @@ struct FieldRow {
 #define RPH_FIELD_ROW(T, f) {#T, #f, (unsigned)offsetof(T, f), (unsigned)sizeof(T::f)},
 #define RPH_STRUCT_ROWS(T) RPH_FIELDS_##T(RPH_FIELD_ROW, T)
 constexpr FieldRow kFieldRows[] = {RPH_DESCRIPTORS(RPH_STRUCT_ROWS)};
+constexpr FieldRow kFieldRowsExt[] = {RPH_DESCRIPTORS_EXT(RPH_STRUCT_ROWS)};
 
 // The listed fields of `strct` start at 0, follow each other with no gap and
 // end at `size`: with no implicit padding in the struct, none is left out.
@@ -71,20 +80,24 @@ constexpr bool layout_same(const char* a, const char* b) {
   for (; *a && *a == *b; ++a, ++b) {}
   return *a == *b;
 }
-constexpr bool layout_covers(const char* strct, size_t size) {
+template <size_t N>
+constexpr bool layout_covers(const FieldRow (&rows)[N], const char* strct, size_t size) {
   size_t end = 0;
-  for (const FieldRow& r : kFieldRows)
+  for (const FieldRow& r : rows)
     if (layout_same(r.strct, strct)) {
       if (r.offset != end) return false;
       end += r.size;
     }
   return end == size;
 }
-#define RPH_STRUCT_COVERED(T)                                                                  \
-  static_assert(layout_covers(#T, sizeof(T)), "RPH_FIELDS_" #T " does not cover " #T           \
-                                              ": a field is missing or out of order, or the " \
-                                              "struct has implicit padding");
+#define RPH_STRUCT_COVERED_IN(rows, T)                                                         \
+  static_assert(layout_covers(rows, #T, sizeof(T)), "RPH_FIELDS_" #T " does not cover " #T     \
+                                                    ": a field is missing or out of order, or " \
+                                                    "the struct has implicit padding");
+#define RPH_STRUCT_COVERED(T) RPH_STRUCT_COVERED_IN(kFieldRows, T)
+#define RPH_STRUCT_COVERED_EXT(T) RPH_STRUCT_COVERED_IN(kFieldRowsExt, T)
 RPH_DESCRIPTORS(RPH_STRUCT_COVERED)
+RPH_DESCRIPTORS_EXT(RPH_STRUCT_COVERED_EXT)
 
 // Constants, by their names in rphedge/ops/layout.py.
 struct ConstRow {
@@ -97,7 +110,7 @@ struct ConstRow {
 constexpr ConstRow kConstRows[] = {
     // constexpr ints
     RPH_CONST(PMAX) RPH_CONST(MAXIN) RPH_CONST(MAXHOLD) RPH_CONST(MAXHIST) RPH_CONST(EVAL_NSTAT) RPH_CONST(LAG_SLOTS)
-    RPH_CONST(LAG_FLOATS) RPH_CONST(PNL_PPT) RPH_CONST(NETW_FLOATS) RPH_CONST(OPT_FLOATS) RPH_CONST(FIT_FLOATS)
+    RPH_CONST(LAG_FLOATS) RPH_CONST(PNL_PPT) RPH_CONST(OOS_WGS_PER_CU) RPH_CONST(NETW_FLOATS) RPH_CONST(OPT_FLOATS) RPH_CONST(FIT_FLOATS)
     RPH_CONST(DP_SLOTS) RPH_CONST(LM_NPMAX) RPH_CONST(LM_TILE) RPH_CONST(LM_GBLK_MAX) RPH_CONST(LM_OUTG)
     RPH_CONST(LM_OUTG_TAIL) RPH_CONST(LM_RED_OUTG) RPH_CONST(LM_RED) RPH_CONST(LM_PASS_WGS_MAX) RPH_CONST(LM_OG_MAX)
     RPH_CONST(LM_SPEC) RPH_CONST(LM_SLOT) RPH_CONST(LM_DP_WGS) RPH_CONST(LM_DP_FLAGS) RPH_CONST(LM_DP_PITCH)

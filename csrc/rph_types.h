@@ -21,6 +21,7 @@ constexpr int EVAL_NSTAT = 32; // doubles per workgroup in the eval stats slab
 constexpr int LAG_SLOTS = 16;  // lagged schedule: replica rows per rotating accumulator buffer
 constexpr int LAG_FLOATS = 3 * PMAX + 16;  // lagged-update state slot: w, m, v [PMAX] + 16 scalars (hedge_lag.h)
 constexpr int PNL_PPT = 4;     // paths per thread of k_hedge_pnl / k_pnl_finish
+constexpr int OOS_WGS_PER_CU = 8;  // k_hedge_oos: persistent workgroups per CU at most (never more than 256-path tiles)
 
 enum Head : int { HEAD_FREE = 0, HEAD_COMPLEMENT = 1 };
 enum Loss : int { LOSS_MSE = 0, LOSS_PINBALL = 1 };
@@ -487,6 +488,41 @@ struct SimDesc {
   // map_blk = 0: contiguous (path_offset + p)
   long long map_blk;
   long long map_stride;
+};
+
+// Fused simulate-and-hedge of fresh paths (k_hedge_oos, hedge_oos.hip): one
+// thread walks one path of `sim` on the fine grid in registers (the step code
+// of the scans, sim_step.h); at every coarse date t it evaluates that date's
+// network(s) on the values the scan would have stored - (float)S * inv_norm,
+// the running statistic, (float)v - and advances the wealth of the P&L scan,
+//   W <- W g + h (S_{t+1} - S_t g),  g = (float)(B_{t+1} / B_t),  W_0 = wealth0;
+// at the end it forms the payoff from the fine-grid terminal state and writes
+// P&L = W_T - payoff and the statistics (ES_V = W_T, ES_RES = P&L).  Nothing
+// of size [dates][paths] is stored unless the trace is asked for.
+//   sim: model SIM_GBM_ARITH | SIM_GBM_LOG (path_stat: any) | SIM_HESTON,
+//     fp32, contiguous indices (map_blk = 0).  Its output pointers are the
+//     TRACE, null in production: out = trace_s [n_coarse][n_local], out2 =
+//     trace_x (statistic / variance), final_out = trace_final, final2_out =
+//     trace_final2 [n_local]; out3 is unused.
+//   network: (1, 8, 1, COMPLEMENT) | (1, 8, 2, FREE) for the plain GBM scans,
+//     (2, 8, 2, FREE) for GBM + statistic and Heston.
+//   payoff_kind: the k_payoff kinds 1 (call) / 2 (put) on the terminal price
+//     (path_stat: on the terminal statistic), 4 / 5 floating strike
+//     max(+-(S_T - stat_T), 0).
+// Persistent workgroups loop over 256-path tiles; workgroup w writes row w of
+// stats (fp64 sums over all its tiles).
+struct OosDesc {
+  SimDesc sim;
+  const NetWeights* snap;        // [n_dates][2] per-date networks (A at [t][0], B at [t][1])
+  const float* fmu;              // [n_dates][MAXIN] per-date standardisation
+  const float* fisd;
+  const double* bond;            // [n_dates + 1] B_t on the coarse grid
+  float* pnl_out;                // per-path P&L [n_local] (may be null)
+  float* payoff_out;             // trace: per-path payoff [n_local] (may be null)
+  double* stats;                 // [num_wgs][EVAL_NSTAT]
+  float alpha, hold_c, wealth0, strike;
+  int has_b, payoff_kind, n_dates, num_wgs;
+  int nin, h, nout, head;
 };
 
 enum HestonScheme : int { HESTON_EULER = 0, HESTON_QE = 1 };

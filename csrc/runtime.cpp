@@ -53,6 +53,11 @@ extern "C" int rph_layout_fields(const FieldRow** rows) {
   return (int)(sizeof(kFieldRows) / sizeof(kFieldRows[0]));
 }
 
+extern "C" int rph_layout_fields_ext(const FieldRow** rows) {
+  *rows = kFieldRowsExt;
+  return (int)(sizeof(kFieldRowsExt) / sizeof(kFieldRowsExt[0]));
+}
+
 extern "C" int rph_layout_consts(const ConstRow** rows) {
   *rows = kConstRows;
   return (int)(sizeof(kConstRows) / sizeof(kConstRows[0]));

@@ -3,6 +3,8 @@
   run        --config cfg.json [--set key=value ...]   any params dict (pension, SV, European, basket)
   european   [--paths N] [--parity] [--payoff NAME] ...   European Options notebook driver (NAME: asian_call ...)
              [--exercise bermudan [--exercise-every K]]   ... with the right to exercise at every K-th rebalancing date
+  run / european also take the out-of-sample test of the trained hedge:
+             [--oos-paths-log2 M] [--oos-seed S] [--oos-stress key=value ...]   2^M fresh paths (stress: sigma=0.18 ...)
   sts                                                    Single Time Step notebook driver
   sweep      [--sigmas .05,.1,...]                       volatility sweep (Multi Time Step)
   calibrate  --csv prices.csv | --synthetic               CIR calibration (Extra: Stochastic Volatility)
@@ -30,9 +32,31 @@ def _coerce(v: str):
 
 
 def _summary(res) -> dict:
-    return {"phi0": res.phi, "psi0": res.psi, "V0": res.v0, "terminal_pnl": res.terminal_pnl, "VaR": res.var,
-            "summary": {k: v for k, v in res.summary.items() if not isinstance(v, list)},
-            "timings": res.timings}
+    out = {"phi0": res.phi, "psi0": res.psi, "V0": res.v0, "terminal_pnl": res.terminal_pnl, "VaR": res.var,
+           "summary": {k: v for k, v in res.summary.items() if not isinstance(v, list)},
+           "timings": res.timings}
+    if res.out_of_sample is not None:
+        out["out_of_sample"] = res.out_of_sample.as_dict()
+    return out
+
+
+def _oos_args(p):
+    p.add_argument("--oos-paths-log2", type=int, default=None,
+                   help="out-of-sample test of the trained hedge on 2^M fresh paths (0: off)")
+    p.add_argument("--oos-seed", type=int, default=None, help="Sobol scramble seed of the test paths")
+    p.add_argument("--oos-stress", nargs="*", default=None, metavar="key=value",
+                   help="simulate the test paths under other model parameters (sigma=0.18, xi=0.4 ...)")
+
+
+def _oos_params(a) -> dict:
+    out = {}
+    if a.oos_paths_log2 is not None:
+        out["oos_paths_log2"] = a.oos_paths_log2
+    if a.oos_seed is not None:
+        out["oos_seed"] = a.oos_seed
+    if a.oos_stress:
+        out["oos_stress"] = ",".join(a.oos_stress)
+    return out
 
 
 def _plots(res, out_dir):
@@ -53,6 +77,7 @@ def main(argv=None) -> int:
     r.add_argument("--sv", action="store_true")
     r.add_argument("--out", default=None)
     r.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
+    _oos_args(r)
     e = sub.add_parser("european")
     e.add_argument("--paths", type=int, default=3000)
     e.add_argument("--rebalancing", type=float, default=1 / 52)
@@ -64,6 +89,7 @@ def main(argv=None) -> int:
     e.add_argument("--exercise-every", type=int, default=None, help="bermudan: every K-th rebalancing date")
     e.add_argument("--set", nargs="*", default=[])
     e.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
+    _oos_args(e)
     sub.add_parser("sts").add_argument("--no-parity", action="store_true")
     s = sub.add_parser("sweep")
     s.add_argument("--sigmas", default="0.05,0.10,0.15,0.20,0.30")
@@ -85,6 +111,7 @@ def main(argv=None) -> int:
         params.update({k: _coerce(v) for k, v in (kv.split("=", 1) for kv in a.set)})
         if a.out:
             params["save_dir"] = a.out
+        params.update(_oos_params(a))
         res = run_params(params, sv=a.sv)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))
@@ -98,6 +125,7 @@ def main(argv=None) -> int:
             extra["exercise"] = a.exercise
         if a.exercise_every is not None:
             extra["exercise_every"] = a.exercise_every
+        extra.update(_oos_params(a))
         res = european_option(N_paths=a.paths, rebalancing_frequency=a.rebalancing, parity=a.parity, **extra)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))

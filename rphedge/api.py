@@ -55,6 +55,8 @@ class RunResult:
     policy_value: float | None = None       # mean discounted amount paid under that rule: the policy's own price, a
                                             # lower bound of the option value (the paths are risk-neutral)
     tree_price: float | None = None         # binomial tree with the same exercise dates (GBM runs)
+    out_of_sample: object = None            # rphedge.oos.OosResult of the reported hedge on fresh paths
+                                            # (oos_paths_log2 > 0; None: not asked for)
 
     def as_tuple(self):
         return self.phi, self.psi
@@ -237,13 +239,43 @@ class HedgeRun:
             return P.payoff("basket_call", p, c.K / c.Y, weights=w, stream=self.stream, out=out)
         return P.payoff("guarantee", p, c.K, stream=self.stream, out=out)
 
-    def _simulate_paths(self, n: int, offset: int, index_map, into: P.Paths | None, defer: list | None = None
-                        ) -> P.Paths:
+    def _sim_params(self, stress: dict | None):
+        """The parameters the path scans read, with the ``stress`` overrides of
+        :meth:`out_of_sample` (None: the run's own).  Only the simulation sees
+        them: the bond grid, the strike and the normalisation stay the run's."""
+        from types import SimpleNamespace
+
+        from .oos import stress_keys
+
+        c = self.cfg
+        sp = SimpleNamespace(r=c.r, mu=c.mu, sigma=c.sigma, v0=c.v0, s0=c.s0, kappa=c.kappa, theta=c.theta, xi=c.xi,
+                             rho=c.rho)
+        allowed = stress_keys(c.model)
+        for k, v in (stress or {}).items():
+            if k not in allowed:
+                raise ValueError(f"unknown out-of-sample stress key {k!r} for model {c.model!r} "
+                                 f"(simulation parameters: {', '.join(allowed) or 'none'})")
+            if k in ("mu", "r"):   # the drift of the simulated asset (r: the option runs, mu: the pension fund)
+                sp.mu = sp.r = float(v)
+            elif k == "v0":        # (the pension SV runs start the variance at s0)
+                sp.v0 = sp.s0 = float(v)
+            else:
+                setattr(sp, k, float(v))
+        return sp
+
+    def _simulate_paths(self, n: int, offset: int, index_map, into: P.Paths | None, defer: list | None = None,
+                        seeds: tuple | None = None, stress: dict | None = None) -> P.Paths:
         """One model's coarse-grid paths for ``n`` paths from global index
         ``offset`` (``index_map``: the Gram subsample's global blocks;
         ``defer``: single-asset scans only - collect the scan's descriptor
-        instead of launching it, :func:`rphedge.ops.paths.simulate_gbm`)."""
+        instead of launching it, :func:`rphedge.ops.paths.simulate_gbm`).
+
+        ``seeds``: the Sobol scramble seeds (price table, second table) instead
+        of the training paths' (``SEED_W1``, ``SEED_W2``); ``stress``:
+        simulation-parameter overrides (:meth:`_sim_params`)."""
         c, g, dev = self.cfg, self.grid, self.device
+        sp = self._sim_params(stress)
+        s1, s2 = (P.SEED_W1, P.SEED_W2) if seeds is None else (int(seeds[0]), int(seeds[1]))
         fp64 = c.dtype == "fp64"
         kw = dict(device=dev, offset=offset, stream=self.stream, out=into, index_map=index_map)
         if defer is not None:
@@ -251,13 +283,13 @@ class HedgeRun:
             kw["defer"] = defer
         if self.kind == "european":
             if c.model == "heston":
-                p = P.simulate_sv(g, n, c.Y, c.r, c.v0, model="heston", kappa=c.kappa, theta=c.theta, xi=c.xi,
-                                  rho=c.rho, norm=c.Y, fp64=fp64, scheme=c.heston_scheme,
-                                  joint=not c.parity.paired_sobol, **kw)
+                p = P.simulate_sv(g, n, c.Y, sp.r, sp.v0, model="heston", kappa=sp.kappa, theta=sp.theta, xi=sp.xi,
+                                  rho=sp.rho, norm=c.Y, fp64=fp64, scheme=c.heston_scheme,
+                                  joint=not c.parity.paired_sobol, seed1=s1, seed2=s2, **kw)
             else:
                 scheme = "arith" if c.model == "gbm" else "log"
-                p = P.simulate_gbm(g, n, c.Y, c.r, c.sigma, scheme=scheme, norm=c.Y, fp64=fp64,
-                                   path_stat=self.path_stat, **kw)
+                p = P.simulate_gbm(g, n, c.Y, sp.r, sp.sigma, scheme=scheme, norm=c.Y, fp64=fp64,
+                                   path_stat=self.path_stat, seed=s1, **kw)
                 p.stat_feature = bool(c.path_feature)
             # EO normalises BOTH prices by S0 (cell 13: _B_t = B/S0, so psi counts
             # unit bonds); the corrected default quotes the bond in S0 units.
@@ -267,23 +299,26 @@ class HedgeRun:
             na = c.n_assets
             corr = np.full((na, na), c.basket_corr) + np.eye(na) * (1 - c.basket_corr)
             s0 = [c.Y] * na
-            p = P.simulate_basket(g, n, s0, [c.r] * na, [c.sigma] * na, corr, norm=s0, **kw)
+            p = P.simulate_basket(g, n, s0, [sp.r] * na, [sp.sigma] * na, corr, norm=s0, seed=s1, **kw)
             p.bond = g.bond(c.r)
             return p
         if c.model in ("sv_ref", "heston"):
-            p = P.simulate_sv(g, n, c.Y, c.mu, c.s0, model=c.model, a=c.a, b=c.b, c=c.sv_c, kappa=c.kappa,
-                              theta=c.theta, xi=c.xi, rho=c.rho, fp64=fp64, parity_nan=c.parity.sv_sqrt_nan,
+            p = P.simulate_sv(g, n, c.Y, sp.mu, sp.s0, model=c.model, a=c.a, b=c.b, c=c.sv_c, kappa=sp.kappa,
+                              theta=sp.theta, xi=sp.xi, rho=sp.rho, fp64=fp64, parity_nan=c.parity.sv_sqrt_nan,
                               scheme=c.heston_scheme,
                               sv_tscale=0.0 if c.parity.sv_reference_dynamics else c.sv_days_per_year,
-                              joint=not c.parity.paired_sobol, **kw)
+                              joint=not c.parity.paired_sobol, seed1=s1, seed2=s2, **kw)
         else:
-            p = P.simulate_gbm(g, n, c.Y, c.mu, c.sigma, scheme=("log" if c.model == "gbm_log" else "arith"),
-                               fp64=fp64, **kw)
+            p = P.simulate_gbm(g, n, c.Y, sp.mu, sp.sigma, scheme=("log" if c.model == "gbm_log" else "arith"),
+                               fp64=fp64, seed=s1, **kw)
         if c.mortality:
             if into is not None and c.parity.numpy_binomial:
                 raise NotImplementedError("numpy binomial (Q20 parity) runs on the host: not graph-safe")
+            # (the binomial draws' Philox seed follows the second table's: the
+            # training paths' SEED_W2 is also simulate_mortality's own default)
             P.simulate_mortality(p, c.l0, c.c, c.ita, c.N, lambda_fine_index=c.parity.lambda_fine_index,
-                                 fp64=fp64, numpy_binomial=c.parity.numpy_binomial, stream=self.stream)
+                                 fp64=fp64, seed=s2, philox_seed=s2, numpy_binomial=c.parity.numpy_binomial,
+                                 stream=self.stream)
         else:
             p.kind = "pension_nomort"
         p.bond = g.bond(c.r)
@@ -562,9 +597,10 @@ class HedgeRun:
             ind.enqueue(start=date - 1)
         finally:
             ind._fcfg = orig
+        self._resumed = (out_dir, int(date))  # (the later dates' networks live there: out_of_sample)
         res = self.collect()
         res.timings["wall_s"] = time.perf_counter() - t0
-        return res
+        return self._with_oos(res)
 
     def run(self) -> RunResult:
         t0 = time.perf_counter()
@@ -573,7 +609,32 @@ class HedgeRun:
         self.enqueue()
         res = self.collect()
         res.timings["wall_s"] = time.perf_counter() - t0
+        return self._with_oos(res)
+
+    def _with_oos(self, res: RunResult) -> RunResult:
+        """``oos_paths_log2 > 0``: the configured out-of-sample test of the finished run."""
+        c = self.cfg
+        if int(c.oos_paths_log2 or 0) > 0:
+            from .oos import parse_stress
+
+            res.out_of_sample = self.out_of_sample(paths_log2=int(c.oos_paths_log2), seed=c.oos_seed,
+                                                   stress=parse_stress(c.oos_stress))
+            res.summary["out_of_sample_pnl_std"] = res.out_of_sample.std
         return res
+
+    def out_of_sample(self, paths_log2: int | None = None, seed: int | None = None, offset: int = 0,
+                      stress: dict | None = None, fused: bool | None = None, keep_pnl: bool = False,
+                      keep_paths: bool = False):
+        """The trained hedge on paths it has not seen (:func:`rphedge.oos.out_of_sample`):
+        ``2^paths_log2`` fresh paths from Sobol index ``offset`` of the stream
+        scrambled with ``seed`` (default :data:`rphedge.oos.OOS_SEED`), optionally
+        simulated under ``stress``-ed model parameters, hedged with the per-date
+        networks, standardisation, strike and bond grid of this run from the
+        fitted V0.  Valid after ``run()``, ``replay()`` or ``resume()``."""
+        from .oos import out_of_sample
+
+        return out_of_sample(self, paths_log2=paths_log2, seed=seed, offset=offset, stress=stress, fused=fused,
+                             keep_pnl=keep_pnl, keep_paths=keep_paths)
 
     def collect(self) -> RunResult:
         c, w = self.cfg, self.di.world

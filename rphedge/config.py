@@ -193,6 +193,11 @@ class RunConfig:
                                      # rebalancing dates t with t % exercise_every == 0, t < the last) | american
                                      # (= bermudan with exercise_every 1: the American option as the grid refines)
     exercise_every: int = 1          # bermudan: every k-th rebalancing date is an exercise date
+    # out-of-sample test of the trained hedge (HedgeRun.out_of_sample; RunResult.out_of_sample)
+    oos_paths_log2: int = 0          # log2 of the fresh test paths (0: off)
+    oos_seed: int | None = None      # Sobol scramble seed of the test paths (None: rphedge.oos.OOS_SEED)
+    oos_stress: object = None        # simulation-parameter overrides of the test paths: a dict, or "key=value,..."
+                                     # (GBM: sigma, mu / r; Heston: v0, kappa, theta, xi, rho)
     mortality: bool = True
     n_assets: int = 1
     basket_weights: tuple = ()

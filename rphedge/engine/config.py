@@ -206,8 +206,9 @@ class PnlData:
     bond: torch.Tensor             # [n_dates + 1] float64 bank account B_t (device)
     fmu: torch.Tensor              # [n_dates, MAXIN] float32 per-date standardisation (device)
     fisd: torch.Tensor             # [n_dates, MAXIN]
-    w0: torch.Tensor               # [n_local] initial wealth (the fitted V_0)
+    w0: torch.Tensor | None        # [n_local] initial wealth (the fitted V_0); None: the scalar ``wealth0``
     payoff: torch.Tensor           # [n_local] terminal liability
+    wealth0: float = 0.0           # initial wealth of every path when ``w0`` is None (out-of-sample paths)
 
 
 def pnl_fold_factors(bond) -> tuple:

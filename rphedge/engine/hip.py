@@ -604,13 +604,18 @@ class HipBackend(StateBlocks):
             raise RuntimeError("persistent fit kernel: workgroups not co-resident (wait timed out); "
                                "use TrainConfig.step_mode='lag' or 'ticket'")
 
-    def pnl_wgs(self) -> int:
-        return (self.n_local + 256 * PNL_PPT - 1) // (256 * PNL_PPT)
+    def pnl_wgs(self, n_local: int | None = None) -> int:
+        return ((self.n_local if n_local is None else int(n_local)) + 256 * PNL_PPT - 1) // (256 * PNL_PPT)
 
     def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
-            exercise: Exercise | None = None, tau_out=None):
+            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None):
         """Enqueue the self-financing P&L scan (one k_hedge_pnl launch);
-        ``exercise``: with the stopping rule, ``tau_out`` (int32) the exercise dates."""
+        ``exercise``: with the stopping rule, ``tau_out`` (int32) the exercise dates;
+        ``n_local``: the path count of ``data`` when it is not this backend's
+        shard (out-of-sample paths; ``stats`` then has ``pnl_wgs(n_local)`` rows)."""
+        nl = self.n_local if n_local is None else int(n_local)
+        if nl != int(data.payoff.numel()):
+            raise ValueError(f"pnl over {data.payoff.numel()} paths with n_local {nl}")
         n = self.native
         d = n.PnlDesc()
         f0, p0, p1 = data.features(0), data.prices(0), data.prices(1)
@@ -623,19 +628,54 @@ class HipBackend(StateBlocks):
             d.price_ts[k] = (b.data_ptr() - a.data_ptr()) // 4
         d.snap = snap.data_ptr()
         d.fmu, d.fisd, d.bond = data.fmu.data_ptr(), data.fisd.data_ptr(), data.bond.data_ptr()
-        d.w0, d.payoff = data.w0.data_ptr(), data.payoff.data_ptr()
+        d.w0, d.payoff = n.ptr(data.w0), data.payoff.data_ptr()
         d.pnl_out = n.ptr(pnl_out)
         d.stats = stats.data_ptr()
-        d.alpha, d.hold_c, d.wealth0, d.has_b = float(self.spec.alpha), float(hold_c), 0.0, 1 if has_b else 0
-        d.n_local, d.n_dates, d.num_wgs = self.n_local, int(data.n_dates), self.pnl_wgs()
+        wealth0 = float(data.wealth0) if data.w0 is None else 0.0
+        d.alpha, d.hold_c, d.wealth0, d.has_b = float(self.spec.alpha), float(hold_c), wealth0, 1 if has_b else 0
+        d.n_local, d.n_dates, d.num_wgs = nl, int(data.n_dates), self.pnl_wgs(nl)
         d.nin, d.h, d.nout, d.head = self.shape
         if exercise is not None:
             d.ex_kind, d.ex_every, d.ex_strike = L.EX_KINDS[exercise.kind], int(exercise.every), float(exercise.strike)
         if tau_out is not None:
-            assert tau_out.dtype == torch.int32 and tau_out.numel() == self.n_local
+            assert tau_out.dtype == torch.int32 and tau_out.numel() == nl
             d.tau_out = tau_out.data_ptr()
         assert stats.shape[0] == d.num_wgs and snap.shape[0] >= data.n_dates
         n.pnl(d, self.stream)
+
+    def oos_wgs(self, n_local: int) -> int:
+        """Grid of a k_hedge_oos launch over ``n_local`` paths: persistent
+        workgroups, at most OOS_WGS_PER_CU per CU and never more than 256-path tiles."""
+        return int(max(1, min(self.native.oos_max_wgs(), (int(n_local) + 255) // 256)))
+
+    def oos(self, sim, snap, data: PnlData, stats, payoff_kind: int, strike: float, has_b: bool = False,
+            hold_c: float = 0.0, pnl_out=None, payoff_out=None):
+        """Enqueue the fused simulate-and-hedge of fresh paths (one k_hedge_oos
+        launch).  ``sim``: the scan's ``SimDesc`` (``ops.paths.gbm_desc`` /
+        ``sv_desc``; its output pointers are the optional trace); ``data``: the
+        run's standardisation and bond tables and the scalar ``wealth0`` (its
+        path tables are not read); ``stats``: ``[num_wgs, EVAL_NSTAT]`` float64 -
+        its row count is the grid (``oos_wgs``, or fewer to make workgroups loop)."""
+        n = self.native
+        d = n.OosDesc()
+        d.sim = sim
+        nl = int(sim.n_local)
+        d.snap = snap.data_ptr()
+        d.fmu, d.fisd, d.bond = data.fmu.data_ptr(), data.fisd.data_ptr(), data.bond.data_ptr()
+        for name, t in (("pnl_out", pnl_out), ("payoff_out", payoff_out)):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != nl):
+                raise ValueError(f"oos: {name} must be float32 [{nl}]")
+        d.pnl_out, d.payoff_out = n.ptr(pnl_out), n.ptr(payoff_out)
+        if stats.dtype != torch.float64 or stats.dim() != 2 or stats.shape[1] != L.EVAL_NSTAT:
+            raise ValueError(f"oos: stats must be float64 [num_wgs, {L.EVAL_NSTAT}]")
+        d.stats = stats.data_ptr()
+        d.alpha, d.hold_c, d.wealth0, d.strike = float(self.spec.alpha), float(hold_c), float(data.wealth0), float(strike)
+        d.has_b, d.payoff_kind, d.n_dates, d.num_wgs = 1 if has_b else 0, int(payoff_kind), int(data.n_dates), int(stats.shape[0])
+        d.nin, d.h, d.nout, d.head = self.shape
+        if snap.shape[0] < data.n_dates or data.fmu.shape[0] < data.n_dates or data.bond.numel() < data.n_dates + 1:
+            raise ValueError("oos: snapshot / standardisation / bond tables shorter than n_dates")
+        n.oos(d, self.stream)
+        return d
 
     def pnl_finish(self, acc, w0, payoff, carry: float, stats, pnl_out=None):
         """Enqueue k_pnl_finish after the eval of date 0 of a run whose evals

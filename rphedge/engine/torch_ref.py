@@ -181,12 +181,16 @@ class TorchBackend(StateBlocks):
         return 1
 
     def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
-            exercise: Exercise | None = None, tau_out=None):
-        """Self-financing P&L scan (reference semantics of k_hedge_pnl)."""
+            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None):
+        """Self-financing P&L scan (reference semantics of k_hedge_pnl;
+        ``n_local``: accepted like HipBackend.pnl's, the path count is the data's)."""
         spec, dt, P = self.spec, torch.float32, self.spec.nparams
         bond = data.bond.detach().cpu().double().numpy()
         fmu, fisd = data.fmu.detach().cpu(), data.fisd.detach().cpu()
-        wealth = data.w0.to(dt).clone()
+        if data.w0 is not None:
+            wealth = data.w0.to(dt).clone()
+        else:  # (PnlDesc.wealth0 with a null w0: every path starts at the scalar)
+            wealth = torch.full(data.payoff.shape, float(data.wealth0), dtype=dt, device=data.payoff.device)
         nd = int(data.n_dates)
         if exercise is not None and has_b:
             raise ValueError("pnl: has_b with exercise (early exercise takes one network)")

@@ -8,6 +8,7 @@ MAXHOLD = 8        # max hedging instruments (assets + bond)
 MAXHIST = 1024
 EVAL_NSTAT = 32
 PNL_PPT = 4        # paths per thread of k_hedge_pnl / k_pnl_finish
+OOS_WGS_PER_CU = 8  # k_hedge_oos (OosDesc): persistent workgroups per CU at most
 DP_SLOTS = 4       # depth of the data-parallel mailboxes
 
 # NetWeights: float w[2][PMAX]; float cur; pad[3]

@@ -144,7 +144,23 @@ class SimDesc(C.Structure):
     ]
 
 
+class OosDesc(C.Structure):
+    """k_hedge_oos (csrc/hedge_oos.hip): ``sim`` is the scan of the fresh paths;
+    its output pointers are the optional trace (null in production)."""
+
+    _fields_ = [
+        ("sim", SimDesc), ("snap", VP), ("fmu", VP), ("fisd", VP), ("bond", VP), ("pnl_out", VP),
+        ("payoff_out", VP), ("stats", VP),
+        ("alpha", C.c_float), ("hold_c", C.c_float), ("wealth0", C.c_float), ("strike", C.c_float),
+        ("has_b", C.c_int), ("payoff_kind", C.c_int), ("n_dates", C.c_int), ("num_wgs", C.c_int),
+        ("nin", C.c_int), ("h", C.c_int), ("nout", C.c_int), ("head", C.c_int),
+    ]
+
+
 DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, SimDesc)
+# descriptors of the native library's second field table (csrc/rph_layout.h
+# RPH_DESCRIPTORS_EXT, rph_layout_fields_ext): checked by name at load like the first
+DESCRIPTORS_EXT = (OosDesc,)
 
 # upper-case ints of layout.py that the native table does not hold (Python only)
 PYTHON_ONLY: tuple[str, ...] = ()
@@ -165,6 +181,13 @@ def native_layout(lib) -> tuple[list[tuple[str, str, int, int]], list[tuple[str,
     nf, nc = lib.rph_layout_fields(C.byref(fr)), lib.rph_layout_consts(C.byref(cr))
     return ([(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]],
             [(r.name.decode(), r.value) for r in cr[:nc]])
+
+
+def native_layout_ext(lib) -> list[tuple[str, str, int, int]]:
+    """The library's second field table: the rows of :data:`DESCRIPTORS_EXT`."""
+    fr = C.POINTER(_FieldRow)()
+    nf = lib.rph_layout_fields_ext(C.byref(fr))
+    return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
 
 
 def layout_mismatches(fields, consts, classes=DESCRIPTORS, layout=L) -> list[str]:
@@ -196,6 +219,10 @@ def _bind(lib):
         "rph_last_error": (C.c_char_p, []),
         "rph_layout_fields": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_consts": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
+        "rph_layout_fields_ext": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_oos": (C.c_int, [C.POINTER(OosDesc), VP]),
+        "rph_oos_check": (C.c_int, [C.POINTER(OosDesc)]),
+        "rph_oos_max_wgs": (C.c_int, [C.POINTER(C.c_int)]),
         "rph_device_info": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong),
                                       C.c_char_p, C.c_int]),
         "rph_memset_async": (C.c_int, [VP, C.c_int, C.c_longlong, VP]),
@@ -267,7 +294,8 @@ def load(required: bool | None = None):
             _build.build(debug=v == "debug", asan=v == "asan")
         lib = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         _bind(lib)
-        bad = layout_mismatches(*native_layout(lib))
+        fields, consts = native_layout(lib)
+        bad = layout_mismatches(fields + native_layout_ext(lib), consts, classes=DESCRIPTORS + DESCRIPTORS_EXT)
         if bad:
             raise RuntimeError("native/Python layout mismatch:\n  " + "\n  ".join(bad))
         _lib = lib
@@ -447,6 +475,26 @@ def pnl(desc: PnlDesc, stream=None):
     """Self-financing hedge P&L scan over the rebalancing dates (k_hedge_pnl)."""
     load(required=True)
     _check(_lib.rph_pnl(C.byref(desc), stream_handle(stream)), "rph_pnl")
+
+
+def oos(desc: OosDesc, stream=None):
+    """Fused simulate-and-hedge of fresh paths (k_hedge_oos)."""
+    load(required=True)
+    _check(_lib.rph_oos(C.byref(desc), stream_handle(stream)), "rph_oos")
+
+
+def oos_check(desc: OosDesc):
+    """The descriptor checks of :func:`oos` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_oos_check(C.byref(desc)), "rph_oos")
+
+
+def oos_max_wgs() -> int:
+    """Workgroups a k_hedge_oos launch may use on the current device (OOS_WGS_PER_CU per CU)."""
+    lib = load(required=True)
+    v = C.c_int()
+    _check(lib.rph_oos_max_wgs(C.byref(v)), "rph_oos_max_wgs")
+    return int(v.value)
 
 
 def pnl_finish(desc: PnlFinishDesc, stream=None):

@@ -136,6 +136,53 @@ def _desc(model, n_local, offset, grid: Grid, fp64, parity, index_map=None):
     return d
 
 
+def gbm_desc(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, scheme: str, norm: float, dev,
+             offset: int = 0, fp64: bool = False, seed: int = SEED_W1, index_map=None, path_stat: str | None = None):
+    """The GBM scan's descriptor without output buffers (:func:`simulate_gbm`
+    attaches them; the fused out-of-sample kernel simulates without any)."""
+    sv, sh, dims = device_table(grid.n_fine, seed, dev)
+    d = _desc(L.SIM_GBM_LOG if scheme == "log" else L.SIM_GBM_ARITH, n_local, offset, grid, fp64, False, index_map)
+    d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), dims
+    d.s0[0], d.mu[0], d.sigma[0], d.inv_norm[0] = s0, mu, sigma, 1.0 / norm
+    if path_stat is not None:
+        d.path_stat = L.PATH_STATS[path_stat]
+    return d
+
+
+def sv_desc(grid: Grid, n_local: int, s0: float, mu: float, v0: float, model: str, a, b, c, kappa, theta, xi, rho,
+            norm: float, dev, offset: int, fp64: bool, parity_nan: bool, seed1: int, seed2: int, scheme: str,
+            sv_tscale: float, joint: bool, index_map=None):
+    """The SV / Heston scan's descriptor without output buffers (``scheme`` and
+    ``joint`` as :func:`simulate_sv` resolved them)."""
+    mcode = L.SIM_SV_REF if model == "sv_ref" else L.SIM_HESTON
+    d = _desc(mcode, n_local, offset, grid, fp64, parity_nan, index_map)
+    nf = grid.n_fine
+    if joint:
+        # ONE Sobol sequence of 2 n_fine dimensions: price shocks at dims
+        # [0, nf), variance shocks at [nf, 2 nf) - jointly equidistributed
+        sv, sh, dd = device_table(2 * nf, seed1, dev)
+        d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), nf
+        d.sv2, d.shift2, d.dims2 = sv.data_ptr() + nf * 32 * 4, sh.data_ptr() + nf * 4, nf
+    else:
+        sv1, sh1, d1 = device_table(nf, seed1, dev)
+        sv2, sh2, d2 = device_table(nf, seed2, dev)
+        d.sv1, d.shift1, d.dims1 = sv1.data_ptr(), sh1.data_ptr(), d1
+        d.sv2, d.shift2, d.dims2 = sv2.data_ptr(), sh2.data_ptr(), d2
+    d.s0[0], d.mu[0], d.inv_norm[0] = s0, mu, 1.0 / norm
+    d.v0, d.a, d.b, d.c = v0, a, b, c
+    d.kappa, d.theta, d.xi, d.rho = kappa, theta, xi, rho
+    d.sv_tscale = float(sv_tscale) if model == "sv_ref" else 0.0
+    d.scheme = L.HESTON_QE if scheme == "qe" else L.HESTON_EULER
+    return d
+
+
+def heston_scheme(scheme: str, kappa: float, xi: float) -> str:
+    """The Heston scheme a scan runs: QE needs a mean-reverting, stochastic variance."""
+    if scheme not in ("qe", "euler"):
+        raise ValueError(f"heston scheme must be qe | euler, got {scheme!r}")
+    return scheme if (scheme == "euler" or (kappa > 0 and xi > 0)) else "euler"
+
+
 def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, scheme: str = "arith",
                  norm: float = 1.0, device="cuda", offset: int = 0, fp64: bool = False, seed: int = SEED_W1,
                  stream=None, out: Paths | None = None, index_map=None, path_stat: str | None = None,
@@ -173,14 +220,9 @@ def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, s
     if _dev_is_gpu(dev):
         from . import native
 
-        sv, sh, dims = device_table(grid.n_fine, seed, dev)
-        d = _desc(L.SIM_GBM_LOG if scheme == "log" else L.SIM_GBM_ARITH, n_local, offset, grid, fp64, False,
-                  index_map)
-        d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), dims
-        d.s0[0], d.mu[0], d.sigma[0], d.inv_norm[0] = s0, mu, sigma, 1.0 / norm
+        d = gbm_desc(grid, n_local, s0, mu, sigma, scheme, norm, dev, offset, fp64, seed, index_map, path_stat)
         d.out, d.final_out = S.data_ptr(), fin.data_ptr()
         if path_stat is not None:
-            d.path_stat = L.PATH_STATS[path_stat]
             d.out2, d.final2_out = A.data_ptr(), afin.data_ptr()
         if defer is not None:
             defer.append(d)
@@ -239,28 +281,11 @@ def simulate_sv(grid: Grid, n_local: int, s0: float, mu: float, v0: float, model
     S = out.S if out is not None else torch.empty(grid.n_coarse, n_local, dtype=torch.float32, device=dev)
     V = out.vol if out is not None else torch.empty(grid.n_coarse, n_local, dtype=torch.float32, device=dev)
     fin = out.S_final if out is not None else torch.empty(n_local, dtype=torch.float32, device=dev)
-    mcode = L.SIM_SV_REF if model == "sv_ref" else L.SIM_HESTON
     if _dev_is_gpu(dev):
         from . import native
 
-        d = _desc(mcode, n_local, offset, grid, fp64, parity_nan, index_map)
-        nf = grid.n_fine
-        if joint:
-            # ONE Sobol sequence of 2 n_fine dimensions: price shocks at dims
-            # [0, nf), variance shocks at [nf, 2 nf) - jointly equidistributed
-            sv, sh, dd = device_table(2 * nf, seed1, dev)
-            d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), nf
-            d.sv2, d.shift2, d.dims2 = sv.data_ptr() + nf * 32 * 4, sh.data_ptr() + nf * 4, nf
-        else:
-            sv1, sh1, d1 = device_table(nf, seed1, dev)
-            sv2, sh2, d2 = device_table(nf, seed2, dev)
-            d.sv1, d.shift1, d.dims1 = sv1.data_ptr(), sh1.data_ptr(), d1
-            d.sv2, d.shift2, d.dims2 = sv2.data_ptr(), sh2.data_ptr(), d2
-        d.s0[0], d.mu[0], d.inv_norm[0] = s0, mu, 1.0 / norm
-        d.v0, d.a, d.b, d.c = v0, a, b, c
-        d.kappa, d.theta, d.xi, d.rho = kappa, theta, xi, rho
-        d.sv_tscale = float(sv_tscale) if model == "sv_ref" else 0.0
-        d.scheme = L.HESTON_QE if scheme == "qe" else L.HESTON_EULER
+        d = sv_desc(grid, n_local, s0, mu, v0, model, a, b, c, kappa, theta, xi, rho, norm, dev, offset, fp64,
+                    parity_nan, seed1, seed2, scheme, sv_tscale, joint, index_map)
         d.out, d.out2, d.final_out = S.data_ptr(), V.data_ptr(), fin.data_ptr()
         if defer is not None:
             defer.append(d)

@@ -40,8 +40,14 @@ def valuation_report(res, discount_rate: float, T: float, eo_artifact: bool = Fa
     v0 = res.v0
     if eo_artifact:  # Q14: the EO notebook discounts values[:,0] instead of the payoff
         disc = v0 * math.exp(-discount_rate * T)
-    return {"V0": v0, "discounted_E_payoff": disc, "difference": v0 - disc,
-            "difference_pct": 100.0 * (v0 - disc) / disc if disc else float("nan")}
+    out = {"V0": v0, "discounted_E_payoff": disc, "difference": v0 - disc,
+           "difference_pct": 100.0 * (v0 - disc) / disc if disc else float("nan")}
+    oos = getattr(res, "out_of_sample", None)
+    if oos is not None:  # the hedge on fresh paths beside its in-sample P&L
+        out["out_of_sample"] = {"pnl_std": oos.std, "pnl_mean": oos.mean, "std_ratio": oos.std_ratio,
+                                "in_sample_pnl_std": oos.in_sample["std"] if oos.in_sample else None,
+                                "n_paths": oos.n_paths, "stress": oos.stress}
+    return out
 
 
 def holdings_over_time(res) -> dict:
@@ -264,6 +270,19 @@ def plot_run(res, paths=None, out_prefix: str = "rphedge_run", max_points: int =
         ax.set_xlabel("t")
         ax.legend()
         _save(plt, fig, files, f"{out_prefix}_exercise_boundary.png")
+    oos = getattr(res, "out_of_sample", None)
+    if oos is not None:
+        # self-financing P&L: in sample vs out of sample (std with the min .. max range)
+        rows = [("out of sample", oos.as_dict())] + ([("in sample", oos.in_sample)] if oos.in_sample else [])
+        fig, ax = plt.subplots()
+        for i, (name, d) in enumerate(rows):
+            ax.bar(i, d["std"], width=0.5, label=f"{name}: std {d['std']:.4g}")
+            ax.plot([i, i], [d["min"], d["max"]], color="k", lw=1)
+        ax.set_xticks(range(len(rows)))
+        ax.set_xticklabels([r[0] for r in rows])
+        ax.set_title(f"hedge P&L on {oos.n_paths} fresh paths" + (f", stress {oos.stress}" if oos.stress else ""))
+        ax.legend()
+        _save(plt, fig, files, f"{out_prefix}_out_of_sample.png")
     if paths is not None:
         files += plot_paths(paths, out_prefix=out_prefix)
     return files

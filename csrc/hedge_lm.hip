@@ -33,9 +33,11 @@
 // [P - NU, P) ONLY: the backward stops at the output layer, the hidden
 // entries [0, P - NU) of its packet rows and of its reduced block are exact
 // zeros, and the kernel carries neither the J tile's LDS nor the Gram code.
+#include <type_traits>
 #include <utility>
 
 #include "hedge_core.h"
+#include "hedge_eval.h"
 #include "hedge_narrow.h"
 
 namespace rph {
@@ -98,7 +100,8 @@ RPH_INLINE constexpr int lm_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 
 // ---------------------------------------------------------------------------
 template <class B>
 __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainDesc d, const LmDesc lm, const int pass,
-                                                                   const double* __restrict__ red_new) {
+                                                                   const double* __restrict__ red_new,
+                                                                   const SelfTargetDesc self) {
   constexpr int P = B::P;
   constexpr int R = B::R;
   constexpr int NR = B::NR;
@@ -113,6 +116,8 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
   __shared__ __attribute__((aligned(16))) float jt[B::FINAL ? 4 : LM_TILE * JP];
   // the output-Gram image of the OG instantiation (the last passes of an lm_out_fix fit)
   __shared__ __attribute__((aligned(16))) unsigned char og_img[B::OGM ? B::OG_LDS : 16];
+  // the target net's image of the self-target instantiation (LmDesc.st_wts)
+  __shared__ __attribute__((aligned(16))) float wt[B::ST_ ? P + 4 : 4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   prefetch_kernarg_end(kat);
   // diagnostic phase stamps of every workgroup but 0 and 1 (tools/stamp_lm.py;
@@ -148,7 +153,11 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
   const bool fin = B::FINAL || pass == lm.passes;
   const typename B::Sched sc =
       B::sched(d, lm.num_wgs, (gram_base > 0 || fin) ? 0 : lm.gram_wgs, lm.gram_skip, lm.leaf_blocks);
-  if (path_wg) B::load(d, 0, perm, sc.b0 * 128, lane, pre);
+  if (path_wg) B::load(d, 0, perm, sc.b0 * 128, lane, pre, &self);
+  if constexpr (B::ST_) {
+    // its own image: lm.w0 (and a renormalised start) make the start point differ from the target net
+    for (int i = tid; i < P; i += 256) wt[i] = self.st_wts->w[0][i];
+  }
   for (int i = tid; i < P; i += 256) {
     float w;
     if (pass == 0) {
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(256, B::WAVES_PER_SIMD) void k_lm_pass(const TrainD
     B::make_frags(wl + S::OW2, fr);
     float val[NR];
     B::partial(d, 0, perm, wl, fr, scratch, pre, val, sc, og_img,
-               lm.slab_o + ((size_t)inst * lm.num_wgs + blockIdx.x) * 3 * 1024);
+               lm.slab_o + ((size_t)inst * lm.num_wgs + blockIdx.x) * 3 * 1024, &self, wt);
 #pragma unroll
     for (int j = 0; j < NR; ++j)
       if (tid + 256 * j < R) slab_b[(size_t)blockIdx.x * R + tid + 256 * j] = val[j];
@@ -962,15 +971,16 @@ RPH_INLINE bool lm_out_newton_w1(const LmOgPre& pre, const float ridge, const fl
 //    system at the damping after m further consecutive rejections (m = 0 is
 //    this solve's own step) — the same arithmetic a later serial solve would
 //    do, so the results are bitwise those of one-solve-per-pass.
+// (the body: workgroup blockIdx.x < LM_SPEC of k_lm_solve or of
+// k_lm_solve_eval; lds: the launch's dynamic LDS)
 template <int P, int R, int NU>
-__global__ __launch_bounds__(256) void k_lm_solve(const TrainDesc d, const LmDesc lm, const double* __restrict__ red_new,
-                                                  const int pass) {
+RPH_INLINE void lm_solve_body(const TrainDesc& d, const LmDesc& lm, const double* __restrict__ red_new, const int pass,
+                              double* const lds) {
   // no implicit fma contraction: every workgroup (own step or a speculative
   // one) must round identically, whatever code copy the compiler makes
 #pragma clang fp contract(off)
   using LS = LmShape<P>;
   constexpr int NB = LS::NB, NBLK = LS::NBLK;
-  extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ int s_fail;
   __shared__ double s_diag;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1394,6 +1404,36 @@ __global__ __launch_bounds__(256) void k_lm_solve(const TrainDesc d, const LmDes
 #undef RPH_STAMPS
 }
 
+template <int P, int R, int NU>
+__global__ __launch_bounds__(256) void k_lm_solve(const TrainDesc d, const LmDesc lm, const double* __restrict__ red_new,
+                                                  const int pass) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  lm_solve_body<P, R, NU>(d, lm, red_new, pass, lds);
+}
+
+// The solve of pass 0 of a later date's main fit with the PREVIOUS date's
+// eval riding in the same launch: workgroups [0, LM_SPEC) are the solve
+// (first in dispatch order, so the factorisation starts at once), the
+// gridDim.x - LM_SPEC workgroups after them are riders that share the blocks
+// of the eval grid (EvalBody::ride) on the CUs the solve leaves idle.  The
+// eval has no reader inside this fit: pass 0 evaluated its own target
+// (NarrowPairBody ST), the statistics, pnl_acc and the snapshot are read by
+// the next date's eval, k_pnl_finish or the host.  The riders use static LDS
+// of their own; every workgroup carries the solve's dynamic LDS (one per CU).
+template <int P, int R, int NU, class E>
+__global__ __launch_bounds__(256) void k_lm_solve_eval(const TrainDesc d, const LmDesc lm,
+                                                       const double* __restrict__ red_new, const int pass,
+                                                       const EvalDesc ev) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  if (blockIdx.x < LM_SPEC) {
+    lm_solve_body<P, R, NU>(d, lm, red_new, pass, lds);
+    return;
+  }
+  __shared__ double sst[4][EVAL_NSTAT];
+  __shared__ __attribute__((aligned(16))) float wl[E::WL_FLOATS];
+  E::ride(ev, (int)blockIdx.x - LM_SPEC, (int)gridDim.x - LM_SPEC, wl, sst);
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1405,6 +1445,11 @@ struct LmKernels {
   // the same body + the full-batch output-layer Gram on the matrix cores (the
   // last LM_OUTG_TAIL passes of an lm_out_fix fit)
   using BodyOG = NarrowPairBody<NIN, H, NO, HEAD, true>;
+  // pass 0 of a later date evaluating its own target (SelfTargetDesc): the
+  // nets whose plain body runs two waves per SIMD, and only while the
+  // self-target body keeps that (256 VGPRs, no scratch: profiles/eval_ride/resource_usage.txt)
+  static constexpr bool HAS_ST = Body::WAVES_PER_SIMD == 2 && HEAD == HEAD_FREE;
+  using BodyST = NarrowPairBody<NIN, H, NO, HEAD, false, HAS_ST>;
   using S = NetShape<NIN, H, NO, HEAD>;
   // the tile store + vectors + hand-off counters (lm_chol.h).  (6, 8, 7):
   // P = 191, 78 tiles of the tile store = 156 KB of the CU's 160 KB; larger nets
@@ -1467,9 +1512,22 @@ static int lm_validate(const TrainDesc* d, const LmDesc* lm, int P, int R, int n
   return 0;
 }
 
+// self-target pass 0 (SelfTargetDesc with st_out set)
+static int lm_validate_st(const TrainDesc* d, const LmDesc* lm, const SelfTargetDesc* st) {
+  if (!st->st_wts || st->st_out != d->target) return rph_report("rph_lm", "st_out: needs st_wts and st_out == target");
+  if (lm->renorm || lm->explore || lm->inst != 1 || lm->weights_only || lm->passes < 1 || d->loss != LOSS_MSE)
+    return rph_report("rph_lm", "st_out: one main MSE fit with passes >= 1, no renorm");
+  for (int f = 0; f < d->nin; ++f)
+    if (!st->st_feat[f] || !(st->st_fisd[f] > 0.f && st->st_fisd[f] < 3.0e38f && st->st_fmu[f] == st->st_fmu[f]))
+      return rph_report("rph_lm", "st_out: null st_feat / bad st_fmu, st_fisd");
+  return 0;
+}
+
 template <int A, int B, int C, int E>
-static int lm_pass_launch(const TrainDesc* d, const LmDesc* lm, int pass, const double* red_new, hipStream_t s) {
+static int lm_pass_launch(const TrainDesc* d, const LmDesc* lm, int pass, const double* red_new, hipStream_t s,
+                          const SelfTargetDesc* stp) {
   using K = LmKernels<A, B, C, E>;
+  const SelfTargetDesc st = stp != nullptr ? *stp : SelfTargetDesc{};
   // path workgroups + Gram-only workgroups past them (Gram subsample > 64 x path grid)
   const bool og = lm->out_gram && pass > lm->passes - LM_OUTG_TAIL;
   // (the final evaluation builds no Gram tile: the path grid alone)
@@ -1479,11 +1537,20 @@ static int lm_pass_launch(const TrainDesc* d, const LmDesc* lm, int pass, const 
     // the last LM_OUTG_TAIL evaluations of an lm_out_fix fit build the output Gram
     if (og) {
       hipLaunchKernelGGL((k_lm_pass<typename K::BodyOG>), dim3(grid, lm->inst), dim3(256), 0, s, *d, *lm, pass,
-                         red_new);
+                         red_new, st);
       return (int)hipGetLastError();
     }
   }
-  hipLaunchKernelGGL((k_lm_pass<typename K::Body>), dim3(grid, lm->inst), dim3(256), 0, s, *d, *lm, pass, red_new);
+  if (st.st_out != nullptr && pass == 0) {
+    if constexpr (K::HAS_ST) {
+      hipLaunchKernelGGL((k_lm_pass<typename K::BodyST>), dim3(grid, lm->inst), dim3(256), 0, s, *d, *lm, pass,
+                         red_new, st);
+      return (int)hipGetLastError();
+    } else {
+      return rph_report("rph_lm", "st_out: no self-target pass body for this network shape");
+    }
+  }
+  hipLaunchKernelGGL((k_lm_pass<typename K::Body>), dim3(grid, lm->inst), dim3(256), 0, s, *d, *lm, pass, red_new, st);
   return (int)hipGetLastError();
 }
 
@@ -1764,17 +1831,22 @@ static LmDesc lm_pass_desc(const LmDesc& lm, const int pass) {
 }
 
 // One pass = pass kernel + reduce kernel (into red_new); the caller all-reduces
-// red_new when data parallel, then launches rph_lm_solve.
-extern "C" int rph_lm_eval(const TrainDesc* d, const LmDesc* lm, double* red_new, int pass, void* stream) {
+// red_new when data parallel, then launches rph_lm_solve.  st (may be null;
+// st_out set): pass 0 evaluates its own target (k_lm_pass<BodyST>).
+extern "C" int rph_lm_eval_st(const TrainDesc* d, const LmDesc* lm, const SelfTargetDesc* st, double* red_new,
+                              int pass, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (st != nullptr && st->st_out == nullptr) st = nullptr;
   int rc = 0;
   if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
         using T = decltype(t);
         using K = LmKernels<T::NIN, T::H, T::NO, T::HEAD>;
         constexpr int P = K::S::P, R = K::S::R, NU = K::Body::NU, NBLK = LmShape<P>::NBLK;
         if (int rc = lm_validate(d, lm, P, R, NBLK, NU)) return rc;
+        if (st != nullptr)
+          if (int rc = lm_validate_st(d, lm, st)) return rc;
         const LmDesc lp = lm_pass_desc<K>(*lm, pass);
-        if (int rc = lm_pass_launch<T::NIN, T::H, T::NO, T::HEAD>(d, &lp, pass, red_new, s)) return rc;
+        if (int rc = lm_pass_launch<T::NIN, T::H, T::NO, T::HEAD>(d, &lp, pass, red_new, s, st)) return rc;
         const int ngw = lm_gram_red_wgs(NBLK * 1024, lp.gram_wgs);
         // the final evaluation built no Gram: its reduce starts past the Gram workgroups
         const int wg0 = pass == lp.passes ? ngw : 0;
@@ -1784,6 +1856,10 @@ extern "C" int rph_lm_eval(const TrainDesc* d, const LmDesc* lm, double* red_new
       }))
     return rc;
   return rph_report("rph_lm_eval", "no LM solver for this network shape (8-unit nets only)");
+}
+
+extern "C" int rph_lm_eval(const TrainDesc* d, const LmDesc* lm, double* red_new, int pass, void* stream) {
+  return rph_lm_eval_st(d, lm, nullptr, red_new, pass, stream);
 }
 
 extern "C" int rph_lm_solve(const TrainDesc* d, const LmDesc* lm, const double* red_new, int pass, void* stream) {
@@ -1810,11 +1886,106 @@ extern "C" int rph_lm_solve(const TrainDesc* d, const LmDesc* lm, const double* 
   return rph_report("rph_lm_solve", "no LM solver for this network shape");
 }
 
+// The solve of `pass` with the eval `ev` riding in the same launch on
+// `riders` extra workgroups (k_lm_solve_eval): one main fit (grid y = 1), one
+// network, no exercise date.  ev->num_wgs is the eval's grid of blocks, as in
+// rph_eval; the riders share them.
+extern "C" int rph_lm_solve_eval(const TrainDesc* d, const LmDesc* lm, const double* red_new, int pass,
+                                 const EvalDesc* ev, int riders, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!ev || !ev->wa || !ev->stats || ev->n_local < 1 || ev->num_wgs < 1 || riders < 1 || riders > 4096)
+    return rph_report("rph_lm_solve_eval", "bad eval descriptor / rider count");
+  if ((long long)(ev->num_wgs - 1) * 256 >= ev->n_local) return rph_report("rph_lm_solve_eval", "eval grid larger than the paths");
+  if (ev->wb || ev->g_base || ev->ex_kind != EX_NONE) return rph_report("rph_lm_solve_eval", "one network, no exercise date");
+  if (ev->nin != d->nin || ev->h != d->h || ev->nout != d->nout || ev->head != d->head)
+    return rph_report("rph_lm_solve_eval", "eval and fit of different network shapes");
+  if (lm->inst != 1 || lm->explore) return rph_report("rph_lm_solve_eval", "the main fit's solve only");
+  if (!(ev->alpha >= 0.f && ev->alpha <= 1.f)) return rph_report("rph_lm_solve_eval", "LeakyReLU slope must be in [0, 1]");
+  for (int f = 0; f < ev->nin; ++f)
+    if (!ev->feat[f] || !(ev->fisd[f] > 0.f && ev->fisd[f] < 3.0e38f && ev->fmu[f] == ev->fmu[f]))
+      return rph_report("rph_lm_solve_eval", "null feature pointer / bad standardisation");
+  const int nhold = ev->head == HEAD_COMPLEMENT ? 2 : ev->nout;
+  bool alias = ev->nin >= nhold - 1;
+  for (int k = 0; alias && k < nhold - 1; ++k) alias = ev->price_t[k] == ev->feat[k];
+  for (int k = 0; k < nhold - 1; ++k)
+    if (!ev->price_t[k] || (ev->pnl_acc && !ev->price_t1[k]))
+      return rph_report("rph_lm_solve_eval", "null price pointer");
+  if (ev->pnl_acc && (!(fabsf(ev->pnl_grow) <= 3.0e38f) || !(fabsf(ev->pnl_carry) <= 3.0e38f)))
+    return rph_report("rph_lm_solve_eval", "pnl_grow / pnl_carry must be finite");
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        using K = LmKernels<T::NIN, T::H, T::NO, T::HEAD>;
+        // (the nets whose pass 0 can evaluate its own target: the others' evals have a reader)
+        if constexpr (!K::HAS_ST) {
+          return rph_report("rph_lm_solve_eval", "no self-target pass body for this network shape");
+        } else {
+        const int bytes = K::smem();
+        auto launch = [&](auto pa) {
+          using E = EvalBody<T::NIN, T::H, T::NO, T::HEAD, decltype(pa)::value, false>;
+          constexpr auto kernel = k_lm_solve_eval<K::S::P, K::S::R, K::Body::NU, E>;
+          static bool attr = false;  // per instantiation
+          if (!attr) {
+            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (e != hipSuccess) {
+              (void)hipGetLastError();
+              return rph_report("rph_lm_solve_eval", "dynamic LDS request refused");
+            }
+            attr = true;
+          }
+          hipLaunchKernelGGL(kernel, dim3(LM_SPEC + riders, 1), dim3(256), bytes, s, *d, *lm, red_new, pass, *ev);
+          return (int)hipGetLastError();
+        };
+        if constexpr (T::NIN >= T::S::NHOLD - 1) {
+          if (alias) return launch(std::true_type{});
+        }
+        return launch(std::false_type{});
+        }
+      }))
+    return rc;
+  return rph_report("rph_lm_solve_eval", "no LM solver for this network shape");
+}
+
+// Self-target pass bodies: 1 where rph_lm_eval_st accepts a SelfTargetDesc for the shape.
+extern "C" int rph_lm_has_st(int nin, int h, int nout, int head) {
+  int has = 0;
+  match_shape(NarrowShapes{}, nin, h, nout, head, &has, [](auto t) {
+    using T = decltype(t);
+    return LmKernels<T::NIN, T::H, T::NO, T::HEAD>::HAS_ST ? 1 : 0;
+  });
+  return has;
+}
+
+// Dynamic LDS of the shape's solve launch in bytes (0: no LM solver): every
+// workgroup of k_lm_solve_eval carries it, so it bounds the riders per CU.
+extern "C" int rph_lm_solve_lds(int nin, int h, int nout, int head) {
+  int bytes = 0;
+  match_shape(NarrowShapes{}, nin, h, nout, head, &bytes, [](auto t) {
+    using T = decltype(t);
+    return LmKernels<T::NIN, T::H, T::NO, T::HEAD>::smem();
+  });
+  return bytes;
+}
+
 // Whole single-rank fit: passes + 1 evaluations, each followed by a solve.
-extern "C" int rph_lm_fit(const TrainDesc* d, const LmDesc* lm, double* red_new, void* stream) {
+// ev != nullptr: the previous date's eval rides in the first solve's launch
+// on `riders` workgroups (rph_lm_solve_eval) and pass 0 evaluates its own
+// target as `st` says.
+extern "C" int rph_lm_fit_ride(const TrainDesc* d, const LmDesc* lm, double* red_new, const SelfTargetDesc* st,
+                               const EvalDesc* ev, int riders, void* stream) {
+  if (ev != nullptr && (st == nullptr || st->st_out == nullptr))
+    return rph_report("rph_lm_fit_ride", "a riding eval needs the self-target pass 0 (its v_out has no other writer)");
   for (int k = 0; k <= lm->passes; ++k) {
-    if (int rc = rph_lm_eval(d, lm, red_new, k, stream)) return rc;
-    if (int rc = rph_lm_solve(d, lm, red_new, k, stream)) return rc;
+    if (int rc = rph_lm_eval_st(d, lm, st, red_new, k, stream)) return rc;
+    if (k == 0 && ev != nullptr) {
+      if (int rc = rph_lm_solve_eval(d, lm, red_new, k, ev, riders, stream)) return rc;
+    } else if (int rc = rph_lm_solve(d, lm, red_new, k, stream)) {
+      return rc;
+    }
   }
   return 0;
+}
+
+extern "C" int rph_lm_fit(const TrainDesc* d, const LmDesc* lm, double* red_new, void* stream) {
+  return rph_lm_fit_ride(d, lm, red_new, nullptr, nullptr, 0, stream);
 }

@@ -3,6 +3,8 @@
 // the step schedules (hedge_mlp.hip, hedge_fit.h, hedge_lag.h) and the
 // Levenberg-Marquardt pass kernel (hedge_lm.hip).
 #pragma once
+#include <type_traits>
+
 #include "hedge_core.h"
 
 namespace rph {
@@ -225,8 +227,17 @@ RPH_INLINE nb_bf16x8 nb_img_frag(const unsigned char* img, int s, int ub, int la
   return __builtin_bit_cast(nb_bf16x8, __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int NIN, int H, int NO, int HEAD, bool OG = false>
+// ST (self-target, pass 0 of a later date's fit; SelfTargetDesc): the target
+// is not loaded but evaluated per path pair - the net of LDS image Wt on the
+// raw features of date t+1 (in Pre in place of y), standardised with that
+// date's (st_fmu, st_fisd), V = sum_k hold_k p_{t+1,k} with the pair's own
+// prices (the fit's prices ARE those of date t+1) - every fma in the order of
+// net_forward and of the V line of k_hedge_eval, so the value is bitwise that
+// kernel's v_out; it serves as y and is stored to st_out for the later passes.
+template <int NIN, int H, int NO, int HEAD, bool OG = false, bool ST = false>
 struct NarrowPairBody {
+  static_assert(!ST || (!OG && HEAD == HEAD_FREE), "self-target: the plain free-head body only");
+  static constexpr bool ST_ = ST;
   // pass workgroups per CU: two for the 1- and 2-input free-head nets without
   // the output Gram (their body fits 256 VGPRs and 46 KB of LDS, so two waves
   // share each SIMD and fill each other's dependency stalls), else one (the
@@ -281,8 +292,14 @@ struct NarrowPairBody {
   static_assert(P - NU == S::OW3, "the output block is [OW3, P)");
   static_assert(4 * NBO * 1024 * 4 <= OG_LDS, "the waves' output-Gram tiles reuse the image LDS");
   struct Frags {};
-  struct Pre {
-    nb_f2 x[NIN], pr[NHOLD], y;
+  struct PreTarget {
+    nb_f2 y;
+  };
+  struct PreSelf {
+    nb_f2 xt[NIN];  // ST: the raw features of date t+1 in place of y
+  };
+  struct Pre : std::conditional_t<ST, PreSelf, PreTarget> {
+    nb_f2 x[NIN], pr[NHOLD];
     nb_f2 m;  // 1: a path of the shard, 0: past its end
   };
 
@@ -312,16 +329,21 @@ struct NarrowPairBody {
     return {GW * gb + (w - GW), TW - GW, nblk};
   }
 
-  RPH_INLINE static void load(const TrainDesc& d, int, const Perm&, long long j0, int lane, Pre& p) {
+  RPH_INLINE static void load(const TrainDesc& d, int, const Perm&, long long j0, int lane, Pre& p,
+                              const SelfTargetDesc* lm = nullptr) {
     const long long ja = j0 + lane, jb = ja + 64;
     const bool va = ja < d.batch, vb = jb < d.batch;
     const long long qa = va ? ja : 0, qb = vb ? jb : 0;
+    if constexpr (ST) {
+#pragma unroll
+      for (int f = 0; f < NIN; ++f) p.xt[f] = nb_f2{lm->st_feat[f][qa], lm->st_feat[f][qb]};
+    }
 #pragma unroll
     for (int f = 0; f < NIN; ++f) p.x[f] = nb_f2{d.feat[f][qa], d.feat[f][qb]};
 #pragma unroll
     for (int k = 0; k < NHOLD - 1; ++k) p.pr[k] = nb_f2{d.price[k][qa], d.price[k][qb]};
     p.pr[NHOLD - 1] = nb_s(d.bond);
-    p.y = nb_f2{d.target[qa], d.target[qb]};
+    if constexpr (!ST) p.y = nb_f2{d.target[qa], d.target[qb]};
     p.m = nb_f2{va ? 1.f : 0.f, vb ? 1.f : 0.f};
   }
 
@@ -400,7 +422,8 @@ struct NarrowPairBody {
   // workgroup's NBO x 1024 output-Gram floats (MFMA register layout)
   RPH_INLINE static void partial(const TrainDesc& d, int step, const Perm& perm, const float* __restrict__ W,
                                  const Frags&, float* lds, Pre& pre, float (&val)[NR], const Sched& sc,
-                                 unsigned char* og_lds = nullptr, float* __restrict__ og_out = nullptr) {
+                                 unsigned char* og_lds = nullptr, float* __restrict__ og_out = nullptr,
+                                 const SelfTargetDesc* lm = nullptr, const float* __restrict__ Wt = nullptr) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const long long stride = sc.bstep * 128;
     const long long jend = sc.bend * 128 < d.batch ? sc.bend * 128 : d.batch;
@@ -458,8 +481,52 @@ struct NarrowPairBody {
       for (int f = 0; f < NIN; ++f) x[f] = (cur.x[f] - d.fmu[f]) * d.fisd[f];
 #pragma unroll
       for (int k = 0; k < NHOLD; ++k) pr[k] = cur.pr[k];
-      const nb_f2 y = cur.y, m = cur.m;
-      if (j0 + stride < jend) load(d, step, perm, j0 + stride, lane, cur);  // the next pair, in flight
+      const nb_f2 m = cur.m;
+      nb_f2 y;
+      [[maybe_unused]] nb_f2 xt[ST ? NIN : 1];
+      if constexpr (ST) {
+#pragma unroll
+        for (int f = 0; f < NIN; ++f) xt[f] = (cur.xt[f] - lm->st_fmu[f]) * lm->st_fisd[f];
+      } else {
+        y = cur.y;
+      }
+      if (j0 + stride < jend) load(d, step, perm, j0 + stride, lane, cur, lm);  // the next pair, in flight
+      if constexpr (ST) {
+        // the target net on date t+1's state: net_forward's chains (one per
+        // unit, inputs in ascending order), then the eval's V chain from 0
+        uint32_t zt = 0;
+        asm volatile("" : "+v"(zt));
+        const float* __restrict__ Wq = (const float*)__builtin_assume_aligned(Wt + (zt & ~3u), 16);
+        nb_f2 t1[H], t2[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          nb_f2 acc = nb_s(Wq[S::OB1 + j]);
+#pragma unroll
+          for (int f = 0; f < NIN; ++f) acc = nb_fma(xt[f], nb_s(Wq[S::OW1 + f * H + j]), acc);
+          t1[j] = nb_lrelu(acc, alpha);
+        }
+#pragma unroll
+        for (int j = 0; j < H; ++j) t2[j] = nb_s(Wq[S::OB2 + j]);
+#pragma unroll
+        for (int i = 0; i < H; ++i)
+#pragma unroll
+          for (int j = 0; j < H; ++j) t2[j] = nb_fma(t1[i], nb_s(Wq[S::OW2 + i * H + j]), t2[j]);
+#pragma unroll
+        for (int j = 0; j < H; ++j) t2[j] = nb_lrelu(t2[j], alpha);
+        nb_f2 Vt = nb_s(0.f);
+#pragma unroll
+        for (int k = 0; k < NO; ++k) {
+          nb_f2 acc = nb_s(Wq[S::OB3 + k]);
+#pragma unroll
+          for (int j = 0; j < H; ++j) acc = nb_fma(t2[j], nb_s(Wq[S::OW3 + j * NO + k]), acc);
+          Vt = nb_fma(acc, pr[k], Vt);
+        }
+        y = Vt;
+        if (m.x != 0.f) lm->st_out[j0 + lane] = y.x;
+        if (m.y != 0.f) lm->st_out[j0 + 64 + lane] = y.y;
+        // the target forward's temporaries die here, before the main body's register peak
+        __builtin_amdgcn_sched_barrier(0);
+      }
 
       // forward
       nb_f2 a1[H], a2[H], o[NO];

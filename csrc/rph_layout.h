@@ -57,11 +57,15 @@ namespace rph {
   X(T, hold_c) X(T, wealth0) X(T, strike) X(T, has_b) X(T, payoff_kind) X(T, n_dates) X(T, num_wgs) X(T, nin)       \
   X(T, h) X(T, nout) X(T, head)
 
+#define RPH_FIELDS_SelfTargetDesc(X, T) X(T, st_feat) X(T, st_wts) X(T, st_out) X(T, st_fmu) X(T, st_fisd)
+
 #define RPH_DESCRIPTORS(X) \
   X(TrainDesc) X(EvalDesc) X(PnlFinishDesc) X(PnlDesc) X(LmDpDesc) X(LmDesc) X(SimDesc)
 // Descriptors of later kernels, in a table of their own (rph_layout_fields_ext;
 // native.py DESCRIPTORS_EXT): checked by name at load exactly like the first.
 #define RPH_DESCRIPTORS_EXT(X) X(OosDesc)
+// ... and of the eval ride (rph_layout_fields_ride; native.py DESCRIPTORS_RIDE)
+#define RPH_DESCRIPTORS_RIDE(X) X(SelfTargetDesc)
 
 struct FieldRow {
   const char* strct;
@@ -73,6 +77,7 @@ struct FieldRow {
 #define RPH_STRUCT_ROWS(T) RPH_FIELDS_##T(RPH_FIELD_ROW, T)
 constexpr FieldRow kFieldRows[] = {RPH_DESCRIPTORS(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsExt[] = {RPH_DESCRIPTORS_EXT(RPH_STRUCT_ROWS)};
+constexpr FieldRow kFieldRowsRide[] = {RPH_DESCRIPTORS_RIDE(RPH_STRUCT_ROWS)};
 
 // The listed fields of `strct` start at 0, follow each other with no gap and
 // end at `size`: with no implicit padding in the struct, none is left out.
@@ -96,8 +101,10 @@ constexpr bool layout_covers(const FieldRow (&rows)[N], const char* strct, size_
                                                     "the struct has implicit padding");
 #define RPH_STRUCT_COVERED(T) RPH_STRUCT_COVERED_IN(kFieldRows, T)
 #define RPH_STRUCT_COVERED_EXT(T) RPH_STRUCT_COVERED_IN(kFieldRowsExt, T)
+#define RPH_STRUCT_COVERED_RIDE(T) RPH_STRUCT_COVERED_IN(kFieldRowsRide, T)
 RPH_DESCRIPTORS(RPH_STRUCT_COVERED)
 RPH_DESCRIPTORS_EXT(RPH_STRUCT_COVERED_EXT)
+RPH_DESCRIPTORS_RIDE(RPH_STRUCT_COVERED_RIDE)
 
 // Constants, by their names in rphedge/ops/layout.py.
 struct ConstRow {

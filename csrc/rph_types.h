@@ -427,6 +427,25 @@ struct LmDesc {
   int pad4;
 };
 
+// Self-target pass 0 of a later date's LM fit (k_lm_pass<BodyST>; an argument
+// of its own beside LmDesc, nullptr / st_out == nullptr: off): the fit's
+// target V_{t+1} = h_{t+1}(state_{t+1}) . p_{t+1} is not read from
+// TrainDesc.target but evaluated by pass 0 itself - the net st_wts on the
+// raw features st_feat of date t+1, standardised with (st_fmu, st_fisd),
+// times the fit's own prices (TrainDesc.price / bond ARE the prices of date
+// t+1) in the operation order of k_hedge_eval, so bitwise its v_out - and
+// stored to st_out (= TrainDesc.target) for the fit's later passes.  The
+// eval of date t+1 then has no reader before the next date and rides in
+// this fit's first solve launch (k_lm_solve_eval).  One main fit only: MSE,
+// no renorm, no exploration, passes >= 1, the nets with a BodyST
+struct SelfTargetDesc {
+  const float* st_feat[MAXIN];
+  const NetWeights* st_wts;
+  float* st_out;
+  float st_fmu[MAXIN];
+  float st_fisd[MAXIN];
+};
+
 // Multi-start selection block (k_lm_select): candidate c = (rank, instance)
 // holds [final best loss, final damping, weights (LM_NPMAX)] at c * LM_SEL_W;
 // packed by every rank into its own segment, summed over the ranks (the LM

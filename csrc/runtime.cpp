@@ -58,6 +58,11 @@ extern "C" int rph_layout_fields_ext(const FieldRow** rows) {
   return (int)(sizeof(kFieldRowsExt) / sizeof(kFieldRowsExt[0]));
 }
 
+extern "C" int rph_layout_fields_ride(const FieldRow** rows) {
+  *rows = kFieldRowsRide;
+  return (int)(sizeof(kFieldRowsRide) / sizeof(kFieldRowsRide[0]));
+}
+
 extern "C" int rph_layout_consts(const ConstRow** rows) {
   *rows = kConstRows;
   return (int)(sizeof(kConstRows) / sizeof(kConstRows[0]));

@@ -413,7 +413,7 @@ class HedgeRun:
                            lm_lam_down=float(tr.lm_lam_down), lm_out_fix=bool(tr.lm_out_fix),
                            lm_out_mu=float(tr.lm_out_mu), lm_out_tr=float(getattr(tr, "lm_out_tr", 0.0)),
                            lm_ridge=float(getattr(tr, "lm_ridge", 1e-10)),
-                           lm_diag_floor=float(tr.lm_diag_floor))
+                           lm_diag_floor=float(tr.lm_diag_floor), eval_ride=bool(getattr(tr, "eval_ride", True)))
         if int(tr.variant) >= 0:
             tcfg.variant = int(tr.variant)
         kw = {}

@@ -404,6 +404,16 @@ class BackwardInduction:
         # the P&L needs every date: a resumed run (start below the last date) reports none
         self.pnl_done = start == nc - 2
         fold = self.pnl_fold and self.pnl_done
+        # eval ride (HipBackend.eval_ride_ok): the eval of a date is not enqueued
+        # on its own but handed to the NEXT date's fit, whose pass 0 evaluates
+        # values[t] itself and whose first solve launch carries the eval; the
+        # eval of date 0 has no later fit and stays a launch of its own.  One
+        # network, no exercise date, warm starts (w_mse stays the fitted net
+        # until the next fit publishes) and a later-date fit that can carry it
+        ride_run = (hasattr(be, "eval_ride_ok") and c.optimizer == "lm" and not c.q99 and c.exercise is None
+                    and c.warm_start and be.eval_ride_ok(self._fcfg(False, L.LOSS_MSE, 0)))
+        self.eval_rides = 0  # evals that rode in a solve launch (this enqueue)
+        pending = None
         for t in self.ran:
             first = t == nc - 2
             pnl_kw = dict(pnl_acc=self.pnl_acc, pnl_grow=float(self.pnl_grow[t]), pnl_carry=float(self.pnl_carry[t]),
@@ -436,8 +446,14 @@ class BackwardInduction:
                                        seed=fit_seed(c.seed, t, 1), poll_every=0)
                     join = torch.cuda.Event()
                     join.record(self._side)
-            be.fit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE, t),
-                   seed=fit_seed(c.seed, t, 0), poll_every=c.poll_every)
+            if pending is not None:
+                be.fit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE, t),
+                       seed=fit_seed(c.seed, t, 0), poll_every=c.poll_every, ride=pending)
+                pending = None
+                self.eval_rides += 1
+            else:
+                be.fit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE, t),
+                       seed=fit_seed(c.seed, t, 0), poll_every=c.poll_every)
             if c.mean_refit and c.optimizer != "lm":
                 be.bias_refit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE))
             hold_out = [self.holdings[t, k] for k in range(self.spec.nhold)] if self.holdings is not None else None
@@ -456,6 +472,10 @@ class BackwardInduction:
                         snap_a=self.snap[t, 0], snap_b=self.snap[t, 1], **pnl_kw)
                 if self.gvalues is not None:
                     self.eval_gram_values(t)
+            elif ride_run and t > 0:
+                # (values[t] is written by pass 0 of date t - 1's fit, bit for bit this eval's v_out)
+                pending = be.eval_desc(self.w_mse, data, s_q, hold_out=hold_out, resid_out=resid_out,
+                                       snap_a=self.snap[t, 0], **pnl_kw)
             else:
                 be.eval(self.w_mse, data, s_q, v_out=self.values[t], hold_out=hold_out, resid_out=resid_out,
                         snap_a=self.snap[t, 0], exercise=self.exercise_at(t), **pnl_kw)

@@ -152,6 +152,11 @@ class TrainConfig:
     # reduced block -> solve, one launch each) even on one rank: the test hook
     # that exercises the RCCL / mailbox exchange path at world size 1
     lm_split: bool = False
+    # later dates of an eligible LM run (HipBackend.eval_ride_ok): the eval of a
+    # date rides in the launch of the next fit's first solve, whose pass 0
+    # evaluates its own target; False forces the sequence fit, eval, fit, ...
+    # with every eval a launch of its own (same results bit for bit)
+    eval_ride: bool = True
     expose_packet: bool = False    # lagged fits: the finalize kernel writes the last step's summed (and
                                    # data-parallel exchanged) gradient packet to HipBackend.grad (tests)
     # optimizer-step schedule on the GPU:

@@ -90,6 +90,8 @@ class HipBackend(StateBlocks):
         self._cache = _Cache()
         self.lm_last_fused = False  # the last LM fit summed its gradient region inside k_lm_reduce
         self._lm_same_gram = True  # the last LM fit built the world-invariant Gram (exchange: gradient region only)
+        # eval ride (eval_ride_ok): shapes whose LM pass 0 can evaluate its own target (k_lm_pass<BodyST>)
+        self._lm_st = self._lm_shape is not None and native.lm_has_st(*self.shape)
 
     def _template(self, fcfg: FitConfig):
         return self._cache.get(("fit", fcfg.key()), lambda: fit_template(fcfg, self.device))
@@ -138,14 +140,21 @@ class HipBackend(StateBlocks):
         d.loss = int(loss)
         return d
 
-    def fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, poll_every: int = 0):
+    def fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, poll_every: int = 0, ride=None):
         """Enqueue a full Keras ``fit`` (epochs x steps).  With ``poll_every``>0 the
         host checks the device early-stop flag every that many epochs and stops
         enqueueing; otherwise everything is asynchronous (graph-capturable) and
-        surplus steps after an early stop are device-side no-ops."""
+        surplus steps after an early stop are device-side no-ops.
+
+        ``ride`` (an :meth:`eval_desc` of the date fitted before, t + 1, whose
+        ``v_out`` is this fit's target; only where :meth:`eval_ride_ok`): that
+        eval is not a launch of its own - pass 0 evaluates the target itself
+        and the eval runs as extra workgroups of the first solve's launch."""
         assert len(data.feats) == self.spec.nin and len(data.prices_next) == self.spec.nhold - 1
         if fcfg.optimizer == "lm":
-            return self._lm_fit(wts, opt, fit, data, fcfg)
+            return self._lm_fit(wts, opt, fit, data, fcfg, ride)
+        if ride is not None:
+            raise ValueError("an eval rides in Levenberg-Marquardt fits only")
         d = self._train_desc(wts, opt, fit, data, fcfg, seed, self._lr(fcfg))
         n, S = self.native, self.steps_per_epoch
         mode = self.step_mode(poll_every)
@@ -321,8 +330,48 @@ class HipBackend(StateBlocks):
         if fused:
             lm.dp = self._cache.get(("lm_dp",), self.lm_mailbox.lm_desc)
 
-    def _lm_prepare(self, wts, opt, fit, data: DateData, fcfg: FitConfig):
-        """The filled (TrainDesc, LmDesc) of a main LM fit; launches nothing and touches no GPU API."""
+    def eval_riders(self) -> int:
+        """Rider workgroups of k_lm_solve_eval: every slot of the device the
+        LM_SPEC solve workgroups leave free, and no more - a rider that waits
+        for a slot runs after the solve instead of under it.  Every workgroup
+        of that launch carries the solve's dynamic LDS and its ~236 VGPRs: two
+        per CU where two of its LDS images fit the CU's 160 KB (the 1-8-8-2
+        net: 70 KB), else one (2-8-8-2: 88 KB).  euro30 with 124 / 252 / 504
+        riders: 5.62 / 4.85 / 4.73 ms against 4.89 without the ride
+        (profiles/eval_ride/bench_ab.txt)."""
+        cus = 256
+        if self.device.type == "cuda":
+            cus = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
+        per_cu = 2 if 2 * (self.native.lm_solve_lds(*self.shape) + 4096) <= 160 * 1024 else 1
+        return max(1, _env("EVAL_RIDERS", per_cu * cus - L.LM_SPEC))
+
+    def eval_ride_ok(self, fcfg: FitConfig) -> bool:
+        """Whether a fit with ``fcfg`` can carry the previous date's eval
+        (:meth:`fit` ``ride``): the switch is on, one rank, an MSE LM fit of a
+        net with a self-target pass body, at least one trial point, launched
+        whole, with no exploration and no start-point transform.  The caller
+        adds what it alone knows: one network, no exercise date, warm starts."""
+        return bool(self.tcfg.eval_ride and _env("EVAL_RIDE", 1) and self._lm_st and self.world == 1
+                    and not self.tcfg.lm_split and fcfg.optimizer == "lm" and int(fcfg.loss) == L.LOSS_MSE
+                    and int(fcfg.epochs) >= 1 and fcfg.lm_renorm is None
+                    and not (int(fcfg.lm_starts) >= 1 and int(fcfg.lm_explore_passes) > 0))
+
+    def _lm_self_target(self, d, ride):
+        """The SelfTargetDesc of pass 0 of a fit (TrainDesc ``d``) that carries the eval ``ride``."""
+        st = self.native.SelfTargetDesc()
+        nh = self.spec.nhold
+        if any(ride.price_t[k] != d.price[k] for k in range(nh - 1)) or float(ride.bond_t) != float(d.bond):
+            raise ValueError("ride: the eval's prices / bond at its date are not this fit's prices_next / bond_next")
+        if ride.v_out not in (None, d.target) or ride.wb or ride.g_base or ride.ex_kind:
+            raise ValueError("ride: one network, no exercise date, v_out the fit's target (or none)")
+        for f in range(self.spec.nin):
+            st.st_feat[f], st.st_fmu[f], st.st_fisd[f] = ride.feat[f], ride.fmu[f], ride.fisd[f]
+        st.st_wts, st.st_out = ride.wa, d.target
+        return st
+
+    def _lm_prepare(self, wts, opt, fit, data: DateData, fcfg: FitConfig, ride=None):
+        """The filled (TrainDesc, LmDesc) of a main LM fit - with ``ride``
+        (TrainDesc, LmDesc, SelfTargetDesc); launches nothing and touches no GPU API."""
         pin = int(fcfg.loss) == L.LOSS_PINBALL
         if int(fcfg.loss) not in (L.LOSS_MSE, L.LOSS_PINBALL):
             raise ValueError(f"no Levenberg-Marquardt fit for loss {fcfg.loss}")
@@ -341,27 +390,38 @@ class HipBackend(StateBlocks):
         if explore:
             lm.lam_carry = 1.0  # the polish starts at the chosen exploration's damping
         self.lm_last_fused = fused  # (transport probe record: which exchange this fit ran)
-        return self._full_batch_desc(wts, opt, fit, data, fcfg, fcfg.loss), lm
+        d = self._full_batch_desc(wts, opt, fit, data, fcfg, fcfg.loss)
+        if ride is not None and not self.eval_ride_ok(fcfg):
+            raise ValueError("this fit cannot carry an eval (eval_ride_ok)")
+        if ride is not None:
+            return d, lm, self._lm_self_target(d, ride)
+        return d, lm
 
-    def _lm_fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig):
+    def _lm_fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, ride=None):
         """Enqueue a full-batch Levenberg-Marquardt fit (MSE): ``fcfg.epochs``
         trial points after the start point, 3 launches each (pass, reduce,
         solve), graph-capturable; data parallel: the gradient region [g |
         stats | out-means] (2.1 KB) is all-reduced between reduce and solve
         (every rank builds the same Gram matrix from the simulated global
         subsample; without it the whole reduced block travels)."""
-        d, lm = self._lm_prepare(wts, opt, fit, data, fcfg)
+        d, lm, *st = self._lm_prepare(wts, opt, fit, data, fcfg, ride)
         if int(fcfg.lm_starts) >= 1 and int(fcfg.lm_explore_passes) > 0:
             self._lm_explore(d, fcfg)
         self._lm_launch(d, lm, self._lm_buffers(fcfg.loss)["red"],
-                        (self.world <= 1 or lm.dp_fused) and not self.tcfg.lm_split, not self._lm_same_gram)
+                        (self.world <= 1 or lm.dp_fused) and not self.tcfg.lm_split, not self._lm_same_gram, ride, st[0] if st else None)
 
-    def _lm_launch(self, d, lm, red, one_launch: bool, gram: bool):
-        """Launch a prepared LM fit: whole, else per trial point pass + reduce, all-reduce (``gram``: with G), solve."""
+    def _lm_launch(self, d, lm, red, one_launch: bool, gram: bool, ride=None, st=None):
+        """Launch a prepared LM fit: whole (``ride``: with that eval in the
+        first solve's launch), else per trial point pass + reduce, all-reduce
+        (``gram``: with G), solve."""
         n = self.native
         if one_launch:
-            n.lm_fit(d, lm, red, self.stream)
+            if ride is not None:
+                n.lm_fit_ride(d, lm, red, st, ride, self.eval_riders(), self.stream)
+            else:
+                n.lm_fit(d, lm, red, self.stream)
             return
+        assert ride is None
         for k in range(lm.passes + 1):
             n.lm_eval(d, lm, red, k, self.stream)
             og = bool(lm.out_gram) and k > lm.passes - L.LM_OUTG_TAIL
@@ -709,6 +769,17 @@ class HipBackend(StateBlocks):
         pnl_grow)`` with the reported holdings (``config.pnl_fold_factors``);
         ``pnl_first``: the first accumulated date writes ``pnl_acc`` without
         reading it.  :meth:`pnl_finish` closes the recursion after date 0."""
+        self.native.eval_(self.eval_desc(wts, data, stats, wts_b=wts_b, g_base=g_base, blend_c=blend_c, hold_c=hold_c,
+                                         v_out=v_out, hold_out=hold_out, resid_out=resid_out, pred1_out=pred1_out,
+                                         snap_a=snap_a, snap_b=snap_b, n_local=n_local, exercise=exercise,
+                                         pnl_acc=pnl_acc, pnl_grow=pnl_grow, pnl_carry=pnl_carry,
+                                         pnl_first=pnl_first), self.stream)
+
+    def eval_desc(self, wts, data: DateData, stats, wts_b=None, g_base=None, blend_c=0.0, hold_c=0.0,
+                  v_out=None, hold_out=None, resid_out=None, pred1_out=None, snap_a=None, snap_b=None,
+                  n_local: int | None = None, exercise: Exercise | None = None, pnl_acc=None, pnl_grow: float = 1.0,
+                  pnl_carry: float = 1.0, pnl_first: bool = False):
+        """The filled descriptor of :meth:`eval` (same arguments); launches nothing."""
         _check_eval_data(self.spec, data)
         n = self.native
         d = n.EvalDesc()
@@ -738,4 +809,4 @@ class HipBackend(StateBlocks):
                 raise ValueError(f"eval: pnl_acc must be float32 [{d.n_local}]")
             d.pnl_acc = pnl_acc.data_ptr()
             d.pnl_grow, d.pnl_carry, d.pnl_first = float(pnl_grow), float(pnl_carry), 1 if pnl_first else 0
-        n.eval_(d, self.stream)
+        return d

@@ -126,6 +126,15 @@ class LmDesc(C.Structure):
         self.inst = 1  # one fit per launch unless a multi-start exploration sets more
 
 
+class SelfTargetDesc(C.Structure):
+    """Pass 0 of an LM fit evaluating its own target (csrc/rph_types.h; ``st_out`` null: off)."""
+
+    _fields_ = [
+        ("st_feat", VP * MAXIN), ("st_wts", VP), ("st_out", VP), ("st_fmu", C.c_float * MAXIN),
+        ("st_fisd", C.c_float * MAXIN),
+    ]
+
+
 class SimDesc(C.Structure):
     _fields_ = [
         ("model", C.c_int), ("n_local", C.c_int), ("path_offset", C.c_longlong),
@@ -161,6 +170,8 @@ DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, Si
 # descriptors of the native library's second field table (csrc/rph_layout.h
 # RPH_DESCRIPTORS_EXT, rph_layout_fields_ext): checked by name at load like the first
 DESCRIPTORS_EXT = (OosDesc,)
+# ... and of its third (RPH_DESCRIPTORS_RIDE, rph_layout_fields_ride): the eval ride
+DESCRIPTORS_RIDE = (SelfTargetDesc,)
 
 # upper-case ints of layout.py that the native table does not hold (Python only)
 PYTHON_ONLY: tuple[str, ...] = ()
@@ -187,6 +198,13 @@ def native_layout_ext(lib) -> list[tuple[str, str, int, int]]:
     """The library's second field table: the rows of :data:`DESCRIPTORS_EXT`."""
     fr = C.POINTER(_FieldRow)()
     nf = lib.rph_layout_fields_ext(C.byref(fr))
+    return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
+
+
+def native_layout_ride(lib) -> list[tuple[str, str, int, int]]:
+    """The library's third field table: the rows of :data:`DESCRIPTORS_RIDE`."""
+    fr = C.POINTER(_FieldRow)()
+    nf = lib.rph_layout_fields_ride(C.byref(fr))
     return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
 
 
@@ -220,6 +238,7 @@ def _bind(lib):
         "rph_layout_fields": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_consts": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
         "rph_layout_fields_ext": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_layout_fields_ride": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_oos": (C.c_int, [C.POINTER(OosDesc), VP]),
         "rph_oos_check": (C.c_int, [C.POINTER(OosDesc)]),
         "rph_oos_max_wgs": (C.c_int, [C.POINTER(C.c_int)]),
@@ -253,6 +272,14 @@ def _bind(lib):
         "rph_lm_eval": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.c_int, VP]),
         "rph_lm_solve": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.c_int, VP]),
         "rph_lm_fit": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, VP]),
+        "rph_lm_fit_ride": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.POINTER(SelfTargetDesc),
+                                      C.POINTER(EvalDesc), C.c_int, VP]),
+        "rph_lm_eval_st": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), C.POINTER(SelfTargetDesc), VP, C.c_int,
+                                     VP]),
+        "rph_lm_solve_eval": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.c_int, C.POINTER(EvalDesc),
+                                        C.c_int, VP]),
+        "rph_lm_has_st": (C.c_int, [C.c_int] * 4),
+        "rph_lm_solve_lds": (C.c_int, [C.c_int] * 4),
         "rph_lm_dp_exchange": (C.c_int, [C.POINTER(LmDpDesc), VP, C.c_int, C.c_int, VP]),
         "rph_lm_select": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, VP, C.c_int, C.c_int, C.c_int,
                                     C.c_int, VP]),
@@ -295,7 +322,8 @@ def load(required: bool | None = None):
         lib = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         _bind(lib)
         fields, consts = native_layout(lib)
-        bad = layout_mismatches(fields + native_layout_ext(lib), consts, classes=DESCRIPTORS + DESCRIPTORS_EXT)
+        bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib), consts,
+                                classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE)
         if bad:
             raise RuntimeError("native/Python layout mismatch:\n  " + "\n  ".join(bad))
         _lib = lib
@@ -439,7 +467,12 @@ def lm_pass_wps(nin: int, h: int, nout: int, head: int) -> int:
     return int(load(required=True).rph_lm_pass_wps(nin, h, nout, head))
 
 
-def lm_eval(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, pass_: int, stream=None):
+def lm_eval(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, pass_: int, stream=None, st=None):
+    """One pass + reduce; ``st`` (:class:`SelfTargetDesc`): pass 0 evaluates its own target."""
+    if st is not None:
+        _check(_lib.rph_lm_eval_st(C.byref(desc), C.byref(lm), C.byref(st), ptr(red_new), int(pass_),
+                                   stream_handle(stream)), "rph_lm_eval_st")
+        return
     _check(_lib.rph_lm_eval(C.byref(desc), C.byref(lm), ptr(red_new), int(pass_), stream_handle(stream)),
            "rph_lm_eval")
 
@@ -453,6 +486,32 @@ def lm_fit(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, stream=None):
     """Whole single-rank Levenberg-Marquardt fit (csrc/hedge_lm.hip), launched from C++."""
     load(required=True)
     _check(_lib.rph_lm_fit(C.byref(desc), C.byref(lm), ptr(red_new), stream_handle(stream)), "rph_lm_fit")
+
+
+def lm_has_st(nin: int, h: int, nout: int, head: int) -> bool:
+    """Whether the shape has a self-target pass body (``SelfTargetDesc``; csrc/hedge_lm.hip LmKernels::HAS_ST)."""
+    return bool(load(required=True).rph_lm_has_st(nin, h, nout, head))
+
+
+def lm_solve_lds(nin: int, h: int, nout: int, head: int) -> int:
+    """Dynamic LDS bytes of the shape's LM solve launch (0: no LM solver)."""
+    return int(load(required=True).rph_lm_solve_lds(nin, h, nout, head))
+
+
+def lm_solve_eval(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, pass_: int, ev: EvalDesc, riders: int,
+                  stream=None):
+    """The solve of ``pass_`` with the eval ``ev`` riding on ``riders`` extra workgroups (k_lm_solve_eval)."""
+    _check(_lib.rph_lm_solve_eval(C.byref(desc), C.byref(lm), ptr(red_new), int(pass_), C.byref(ev), int(riders),
+                                  stream_handle(stream)), "rph_lm_solve_eval")
+
+
+def lm_fit_ride(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, st: SelfTargetDesc, ev: EvalDesc, riders: int,
+                stream=None):
+    """:func:`lm_fit` with pass 0 evaluating its own target (``st``) and the
+    eval ``ev`` riding in the launch of the first solve."""
+    load(required=True)
+    _check(_lib.rph_lm_fit_ride(C.byref(desc), C.byref(lm), ptr(red_new), C.byref(st), C.byref(ev), int(riders),
+                                stream_handle(stream)), "rph_lm_fit_ride")
 
 
 def lm_select(desc: TrainDesc, lm: LmDesc, sel: torch.Tensor, main_state: torch.Tensor, world: int, rank: int,

@@ -19,11 +19,15 @@ def main():
     # ... and closes with the P&L: k_pnl_finish (folded into the evals), or the k_hedge_pnl scan
     end = next(i for i in range(start, len(rows)) if "k_pnl_finish" in rows[i][0] or "k_hedge_pnl" in rows[i][0])
     rep = rows[start:end + 1]
-    first_eval = next(i for i, r in enumerate(rep) if "k_hedge_eval" in r[0])
+    # the first date ends with its k_hedge_eval, or - where that eval rides in the next fit's first solve launch
+    # (k_lm_solve_eval) - before the pass two launches ahead of that solve
+    first_eval = next(i - 2 if "k_lm_solve_eval" in r[0] else i for i, r in enumerate(rep)
+                      if "k_hedge_eval" in r[0] or "k_lm_solve_eval" in r[0])
     agg, cnt = collections.defaultdict(float), collections.Counter()
     for i, (name, t0, t1, gy) in enumerate(rep):
         seg = "explore" if gy > 1 else ("first" if i < first_eval else "later")
         k = name.split("(")[0].replace("_ZN3rph", "").split("E")[0][:24]
+        k = "15k_lm_solve_eval" if "k_lm_solve_eval" in name else k
         agg[(seg, k)] += (t1 - t0) / 1e3
         cnt[(seg, k)] += 1
     print(f"replay {(rep[-1][2] - rep[0][1]) / 1e3:.1f} us, {len(rep)} kernels, first date "

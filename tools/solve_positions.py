@@ -17,14 +17,17 @@ def main():
     # ... and closes with the P&L: k_pnl_finish (folded into the evals), or the k_hedge_pnl scan
     end = next(i for i in range(start, len(rows)) if "k_pnl_finish" in rows[i][0] or "k_hedge_pnl" in rows[i][0])
     rep = rows[start:end + 1]
-    fe = next(i for i, r in enumerate(rep) if "k_hedge_eval" in r[0])
+    # a later date opens after the previous date's k_hedge_eval, or - where that eval rides in the date's first
+    # solve launch (k_lm_solve_eval, counted as k_lm_solve #0) - with the pass two launches before that solve
+    ride = {i - 2 for i, r in enumerate(rep) if "k_lm_solve_eval" in r[0]}
+    fe = min([i for i, r in enumerate(rep) if "k_hedge_eval" in r[0]][:1] + sorted(ride)[:1])
     pos = collections.defaultdict(list)
     cnt = collections.Counter()
-    for name, t0, t1 in rep[fe:]:
+    for i, (name, t0, t1) in enumerate(rep[fe:], fe):
         k = next((x for x in ("k_lm_solve", "k_lm_pass", "k_lm_reduce", "k_hedge_eval") if x in name), None)
         if k is None:
             continue
-        if k == "k_hedge_eval":
+        if k == "k_hedge_eval" or i in ride:
             cnt.clear()
         pos[(k, cnt[k])].append((t1 - t0) / 1e3)
         cnt[k] += 1

@@ -39,6 +39,9 @@
 #include "hedge_core.h"
 #include "hedge_eval.h"
 #include "hedge_narrow.h"
+#include "sim_scan.h"  // sim_scan_block: the riders of k_lm_solve_sim
+
+extern "C" int rph_sim_ride_rest(const rph::SimRideDesc* r, int from, void* stream);  // paths.hip
 
 namespace rph {
 
@@ -1434,6 +1437,43 @@ __global__ __launch_bounds__(256) void k_lm_solve_eval(const TrainDesc d, const 
   E::ride(ev, (int)blockIdx.x - LM_SPEC, (int)gridDim.x - LM_SPEC, wl, sst);
 }
 
+// One slice of a sim ride (SimRideDesc, sim_ride_slice) as the riders of one
+// solve launch see it.
+struct SimRideArg {
+  SimDesc sim;
+  SimPay pay;
+  int start, count;  // the slice: blocks [start, start + count)
+  int riders, per_rider;
+};
+
+// A solve of a first date's exploration with a slice of the run's path scan
+// riding in the same launch: workgroups x < LM_SPEC of every instance (grid y)
+// are the solve, unchanged; the workgroups after them, numbered over x and y,
+// are riders that scan whole 256-path blocks (sim_scan_block + payoff, as in
+// k_sim_scan) on the CUs the solves leave idle.  The exploration reads the
+// blocks the head launch simulated and nothing reads the riders' blocks before
+// this fit has returned: no rider waits for anything.  Riders use no LDS.
+// Riders exist for the scans without a path statistic (sim_rider_for); a
+// sibling of k_lm_solve_eval rather than one template with a rider policy: the
+// two share lm_solve_body and nothing else (arguments, LDS, grid shape differ).
+template <int P, int R, int NU, int MODEL>
+__global__ __launch_bounds__(256) void k_lm_solve_sim(const TrainDesc d, const LmDesc lm,
+                                                      const double* __restrict__ red_new, const int pass,
+                                                      const SimRideArg a) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  if (blockIdx.x < LM_SPEC) {
+    lm_solve_body<P, R, NU>(d, lm, red_new, pass, lds);
+    return;
+  }
+  const int r = (int)blockIdx.y * ((int)gridDim.x - LM_SPEC) + (int)blockIdx.x - LM_SPEC;
+  if (r >= a.riders) return;
+  for (int j = 0; j < a.per_rider; ++j) {
+    const int b = r + j * a.riders;
+    if (b >= a.count) return;
+    sim_scan_block<float, true, MODEL, STAT_NONE, true>(a.sim, a.start + b, a.pay);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1965,6 +2005,102 @@ extern "C" int rph_lm_solve_lds(int nin, int h, int nout, int head) {
     return LmKernels<T::NIN, T::H, T::NO, T::HEAD>::smem();
   });
   return bytes;
+}
+
+// Riders of the sim ride: the single-asset scans of the option runs, on the
+// nets those runs fit - GBM (arithmetic / log) with one input, Heston with two.
+// Scans with a path statistic have no rider (the caller keeps the plain scan).
+template <class T, int MODEL>
+static constexpr bool sim_rider_for() {
+  return (T::NIN == 1 && (MODEL == SIM_GBM_ARITH || MODEL == SIM_GBM_LOG)) || (T::NIN == 2 && MODEL == SIM_HESTON);
+}
+
+// 1 where rph_lm_solve_sim has a rider for the scan (model, path_stat) under the shape's solve.
+extern "C" int rph_lm_has_sim(int nin, int h, int nout, int head, int model, int path_stat) {
+  int has = 0;
+  match_shape(NarrowShapes{}, nin, h, nout, head, &has, [&](auto t) {
+    using T = decltype(t);
+    if (path_stat != STAT_NONE) return 0;
+    return (model == SIM_GBM_ARITH && sim_rider_for<T, SIM_GBM_ARITH>()) ||
+                   (model == SIM_GBM_LOG && sim_rider_for<T, SIM_GBM_LOG>()) ||
+                   (model == SIM_HESTON && sim_rider_for<T, SIM_HESTON>())
+               ? 1
+               : 0;
+  });
+  return has;
+}
+
+// The solve of `pass` of an exploration (any instance count) with slice k of
+// the sim ride r on `riders` rider workgroups (k_lm_solve_sim), spread over the
+// grid's x and y.  An empty slice is an error: the caller launches rph_lm_solve.
+extern "C" int rph_lm_solve_sim(const TrainDesc* d, const LmDesc* lm, const double* red_new, int pass,
+                                const SimRideDesc* r, int riders, int k, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = validate_sim_ride(r, "rph_lm_solve_sim")) return rc;
+  if (riders < 1 || riders > 4096 || r->per_rider > 64 || k < 0)
+    return rph_report("rph_lm_solve_sim", "bad rider count (1..4096) / blocks per rider (1..64) / slice");
+  if (!lm->explore || lm->inst < 1) return rph_report("rph_lm_solve_sim", "the solves of an exploration only");
+  const SimRideSlice sl = sim_ride_slice(r->b0, r->b1, riders, r->per_rider, k);
+  if (sl.count < 1) return rph_report("rph_lm_solve_sim", "empty slice");
+  const SimRideArg arg{r->sim, SimPay{r->pay_out, r->pay_out2, r->strike, r->pay_kind}, sl.start, sl.count, riders,
+                       r->per_rider};
+  const int rx = (riders + lm->inst - 1) / lm->inst;  // rider workgroups per instance row
+  int rc = 0;
+  if (match_shape(NarrowShapes{}, d->nin, d->h, d->nout, d->head, &rc, [&](auto t) {
+        using T = decltype(t);
+        using K = LmKernels<T::NIN, T::H, T::NO, T::HEAD>;
+        const int bytes = K::smem();
+        auto launch = [&](auto m) {
+          constexpr int MODEL = decltype(m)::value;
+          if constexpr (!sim_rider_for<T, MODEL>()) {
+            return rph_report("rph_lm_solve_sim", "no rider for this scan under this network shape");
+          } else {
+            constexpr auto kernel = k_lm_solve_sim<K::S::P, K::S::R, K::Body::NU, MODEL>;
+            static bool attr = false;  // per instantiation
+            if (!attr) {
+              hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+              if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return rph_report("rph_lm_solve_sim", "dynamic LDS request refused");
+              }
+              attr = true;
+            }
+            hipLaunchKernelGGL(kernel, dim3(LM_SPEC + rx, lm->inst), dim3(256), bytes, s, *d, *lm, red_new, pass, arg);
+            return (int)hipGetLastError();
+          }
+        };
+        if (r->sim.path_stat != STAT_NONE) return rph_report("rph_lm_solve_sim", "no rider for scans with a path statistic");
+        switch (r->sim.model) {
+          case SIM_GBM_ARITH: return launch(std::integral_constant<int, SIM_GBM_ARITH>{});
+          case SIM_GBM_LOG: return launch(std::integral_constant<int, SIM_GBM_LOG>{});
+          case SIM_HESTON: return launch(std::integral_constant<int, SIM_HESTON>{});
+          default: return rph_report("rph_lm_solve_sim", "no rider for this scan model");
+        }
+      }))
+    return rc;
+  return rph_report("rph_lm_solve_sim", "no LM solver for this network shape");
+}
+
+// Whole single-rank exploration fit with the sim ride r: solve k carries slice
+// k of the ride's blocks until none are left, the later solves are plain; what
+// the solves could not carry goes out as one plain scan launch behind the last
+// of them.  When this returns every block of [b0, b1) has been enqueued once.
+extern "C" int rph_lm_fit_sim(const TrainDesc* d, const LmDesc* lm, double* red_new, const SimRideDesc* r, int riders,
+                              void* stream) {
+  if (int rc = validate_sim_ride(r, "rph_lm_fit_sim")) return rc;
+  if (riders < 1) return rph_report("rph_lm_fit_sim", "bad rider count");
+  int next = r->b0;
+  for (int k = 0; k <= lm->passes; ++k) {
+    if (int rc = rph_lm_eval_st(d, lm, nullptr, red_new, k, stream)) return rc;
+    const SimRideSlice sl = sim_ride_slice(r->b0, r->b1, riders, r->per_rider, k);
+    if (sl.count > 0) {
+      if (int rc = rph_lm_solve_sim(d, lm, red_new, k, r, riders, k, stream)) return rc;
+      next = sl.start + sl.count;
+    } else if (int rc = rph_lm_solve(d, lm, red_new, k, stream)) {
+      return rc;
+    }
+  }
+  return rph_sim_ride_rest(r, next, stream);
 }
 
 // Whole single-rank fit: passes + 1 evaluations, each followed by a solve.

@@ -13,10 +13,12 @@
 // are regenerated on the fly (W is never stored); only the coarse rebalancing
 // grid (every `reduction` fine steps, RP:92-96) is written, time-major
 // [n_coarse][n_local] so each date is one coalesced row per wave.
+#include <type_traits>
+
 #include "rph_common.h"
 #include "rph_types.h"
 
-#include "sim_step.h"  // the per-step scan code (shared with hedge_oos.hip), ndtri_u30, sim_gidx
+#include "sim_scan.h"  // sim_scan_block (shared with hedge_lm.hip); sim_step.h: the per-step code, ndtri_u30, sim_gidx
 
 namespace rph {
 
@@ -41,138 +43,26 @@ __global__ __launch_bounds__(256) void k_sobol_normal(Real* __restrict__ out, in
 // ---------------------------------------------------------------------------
 // Single-asset / SV / Heston / mortality scans.
 // ---------------------------------------------------------------------------
-// STAT (GBM models only; PathStat in rph_types.h): a running statistic of the
-// FINE-grid path, monitored at the fine points j = 1..t (max / min also at
-// j = 0), kept in a register beside the state and stored to out2 / final2_out
-// exactly like the price.  STAT = 0 is the plain scan.
-// The scan of workgroup `blk` of descriptor d (k_sim_scan: the whole grid one
-// descriptor; k_sim_scan_pair: two descriptors side by side).
-template <typename Real, bool ALIGNED, int MODEL, int STAT>
-RPH_INLINE void sim_scan_block(const SimDesc& d, const int blk) {
-  const int p = blk * 256 + threadIdx.x;
-  if (!ALIGNED && p >= d.n_local) return;
-  const long long gp = sim_gidx(d, p);
-  const uint32_t g = gray_code((uint64_t)gp);
-  const Real dt = (Real)d.dt;
-  const Real sdt = sqrt(dt);
-  const float inv0 = (float)d.inv_norm[0];
-  const size_t n = (size_t)d.n_local;
-
-  if (MODEL == SIM_GBM_ARITH || MODEL == SIM_GBM_LOG) {
-    GbmScan<Real, MODEL, STAT> gs;  // (sim_step.h)
-    gs.init(d);
-    d.out[p] = (float)d.s0[0] * inv0;
-    if (STAT != STAT_NONE) d.out2[p] = (float)d.s0[0] * inv0;
-    for (int t = 1; t < d.n_fine; ++t) {
-      const Real z = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
-      gs.step(z);
-      if (t % d.reduction == 0 || (STAT != STAT_NONE && t == d.n_fine - 1)) gs.refresh(t);
-      if (t % d.reduction == 0) {
-        const int c = t / d.reduction;
-        const Real s = gs.price();
-        if (c < d.n_coarse) {
-          d.out[(size_t)c * n + p] = (float)s * inv0;
-          if (STAT != STAT_NONE) d.out2[(size_t)c * n + p] = (float)gs.stat * inv0;
-        }
-      }
-    }
-    const Real s = gs.price();
-    if (d.final_out) d.final_out[p] = (float)s * inv0;
-    if (STAT != STAT_NONE && d.final2_out) d.final2_out[p] = (float)gs.stat * inv0;
-  } else if (MODEL == SIM_SV_REF || MODEL == SIM_HESTON) {
-    // table 1 -> price shocks (W1, seed 1235), table 2 -> variance shocks (W_SV)
-    SvScan<Real, MODEL> ss;  // (sim_step.h)
-    ss.init(d);
-    d.out[p] = (float)d.s0[0] * inv0;
-    if (d.out2) d.out2[p] = (float)ss.v;
-    for (int t = 1; t < d.n_fine; ++t) {
-      const Real z1 = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
-      const uint32_t x2 = sobol_point<ALIGNED>(d.sv2 + (size_t)t * 32, d.shift2[t], g);
-      ss.step(d, z1, x2);
-      if (t % d.reduction == 0) {
-        const int c = t / d.reduction;
-        if (c < d.n_coarse) {
-          d.out[(size_t)c * n + p] = (float)ss.price() * inv0;
-          if (d.out2) d.out2[(size_t)c * n + p] = (float)ss.v;
-        }
-      }
-    }
-    if (d.final_out) d.final_out[p] = (float)ss.price() * inv0;
-  } else if (MODEL == SIM_MORTALITY) {
-    // RP:73-76 lambda Euler (Sobol seed 1234); RP:78-84 N_t ~ Binom(N_{t-1}, exp(-lambda_t dt)).
-    Real lam = (Real)d.l0;
-    int N = d.n0;
-    const float invn = 1.0f / (float)d.n0;
-    d.out2[p] = 1.0f;
-    if (d.out3) d.out3[p] = (float)lam;
-    const Real lc = (Real)d.lc, eta_sdt = (Real)d.eta * sdt;
-    for (int t = 1; t < d.n_fine; ++t) {
-      const Real z = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv2 + (size_t)t * 32, d.shift2[t], g));
-      lam = lam + (lc * lam * dt + eta_sdt * z);
-      // binomial deaths by inversion (mean N q << 1 per fine step)
-      double q = 1.0 - exp(-(double)lam * (double)dt);
-      q = q < 0.0 ? 0.0 : (q > 1.0 ? 1.0 : q);
-      if (N > 0 && q > 0.0) {
-        const u32x4 r = philox4x32_10({(uint32_t)gp, (uint32_t)(gp >> 32),
-                                       (uint32_t)t, 0xB1A0u},
-                                      d.seed, 0x1234u);
-        const double u = u01d(r.x, r.y);
-        const double mean = (double)N * q;
-        int D;
-        if (mean < 200.0 && q < 1.0) {
-          double f = exp((double)N * log1p(-q));  // P(D = 0)
-          double F = f;
-          const double ratio = q / (1.0 - q);
-          D = 0;
-          while (u > F && D < N) {
-            f *= (double)(N - D) / (double)(D + 1) * ratio;
-            ++D;
-            F += f;
-            if (f < 1e-300 && F < u) { break; }
-          }
-        } else {
-          // N q >= 200 expected deaths in the step (or q = 1): the CDF walk
-          // would take that many iterations per thread, so D is the rounded
-          // normal approximation N q + sqrt(N q (1 - q)) z clipped to [0, N],
-          // z from the top 30 bits of the same uniform (made odd: never 0).
-          // Reached from about 10^5 members at quarterly steps, 10^6 at
-          // dt = 0.01; _cpu_mortality follows the same rule.
-          const double z2n = ndtri_u30<double>((uint32_t)(u * 1073741824.0) | 1u);
-          double dd = mean + sqrt(mean * (1.0 - q)) * z2n + 0.5;
-          dd = dd < 0.0 ? 0.0 : (dd > (double)N ? (double)N : dd);
-          D = (int)dd;
-        }
-        N -= D;
-      }
-      if (d.parity) {  // Q3: lambda is NOT subsampled in the reference (RP:200 uses fine index t_i)
-        if (t < d.n_coarse && d.out3) d.out3[(size_t)t * n + p] = (float)lam;
-      }
-      if (t % d.reduction == 0) {
-        const int c = t / d.reduction;
-        if (c < d.n_coarse) {
-          d.out2[(size_t)c * n + p] = (float)N * invn;
-          if (!d.parity && d.out3) d.out3[(size_t)c * n + p] = (float)lam;
-        }
-      }
-    }
-    if (d.final2_out) d.final2_out[p] = (float)N * invn;
-  }
-}
-
-template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
-__global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d) {
-  sim_scan_block<Real, ALIGNED, MODEL, STAT>(d, (int)blockIdx.x);
+// Workgroup b scans block blk0 + b of d (blk0 > 0: the blocks a split scan has
+// left, rph_sim_ride_rest) and writes the payoff `pay` asks for.
+// WIDE: the low-occupancy step code of sim_scan_block (the parts of a split scan).
+template <typename Real, bool ALIGNED, int MODEL, int STAT = 0, bool WIDE = false>
+__global__ __launch_bounds__(256) void k_sim_scan(const SimDesc d, const int blk0, const SimPay pay) {
+  sim_scan_block<Real, ALIGNED, MODEL, STAT, WIDE>(d, blk0 + (int)blockIdx.x, pay);
 }
 
 // Two scans of the same instantiation in one launch: workgroups [0, split) run
 // descriptor a, the rest descriptor b (the run's paths and the LM Gram
 // subsample: the second is a few workgroups of pure Sobol / ndtri latency,
 // which hide beside the first instead of following it on an empty GPU).  Every
-// thread runs sim_scan_block exactly as in a launch of its own.
-template <typename Real, bool ALIGNED, int MODEL, int STAT = 0>
-__global__ __launch_bounds__(256) void k_sim_scan_pair(const SimDesc a, const SimDesc b, const int split) {
-  if ((int)blockIdx.x < split) sim_scan_block<Real, ALIGNED, MODEL, STAT>(a, (int)blockIdx.x);
-  else sim_scan_block<Real, ALIGNED, MODEL, STAT>(b, (int)blockIdx.x - split);
+// thread runs sim_scan_block exactly as in a launch of its own.  `pay`: the
+// payoff of a's paths (split below a's grid: the head of a split scan,
+// rph_sim_ride_head).
+template <typename Real, bool ALIGNED, int MODEL, int STAT = 0, bool WIDE = false>
+__global__ __launch_bounds__(256) void k_sim_scan_pair(const SimDesc a, const SimDesc b, const int split,
+                                                       const SimPay pay) {
+  if ((int)blockIdx.x < split) sim_scan_block<Real, ALIGNED, MODEL, STAT, WIDE>(a, (int)blockIdx.x, pay);
+  else sim_scan_block<Real, ALIGNED, MODEL, STAT, WIDE>(b, (int)blockIdx.x - split);
 }
 
 // ---------------------------------------------------------------------------
@@ -315,42 +205,62 @@ extern "C" int rph_sobol_normal(void* out, int n, int d, const uint32_t* sv, con
 
 // One scan instantiation: descriptor d alone, or d and d2 side by side in one
 // grid (d2 non-null: k_sim_scan_pair; the mortality scan is never paired).
+// cut (may be null: d's whole grid, no payoff) = {first block, blocks, payoff}
+// of d: a part of a split scan (SimRideDesc).
+struct ScanCut {
+  int blk0, nblk;
+  SimPay pay;
+};
+
 template <typename Real, bool AL, int MODEL, int STAT = 0>
-static void launch_scan_kernel(const SimDesc* d, const SimDesc* d2, hipStream_t s) {
-  const int split = grid_for(d->n_local);
-  if constexpr (MODEL != SIM_MORTALITY) {
-    if (d2) {
-      hipLaunchKernelGGL((k_sim_scan_pair<Real, AL, MODEL, STAT>), dim3(split + grid_for(d2->n_local)), dim3(256), 0, s,
-                         *d, *d2, split);
+static void launch_scan_kernel(const SimDesc* d, const SimDesc* d2, hipStream_t s, const ScanCut* cut = nullptr) {
+  const int split = cut ? cut->nblk : grid_for(d->n_local);
+  const SimPay pay = cut ? cut->pay : SimPay{};
+  if constexpr ((MODEL == SIM_GBM_ARITH || MODEL == SIM_GBM_LOG || MODEL == SIM_HESTON) && STAT == STAT_NONE && AL &&
+                std::is_same<Real, float>::value) {
+    // the parts of a split scan (validate_sim_ride: these scans only) are small grids: the low-occupancy step code
+    if (cut) {
+      if (d2)
+        hipLaunchKernelGGL((k_sim_scan_pair<Real, AL, MODEL, STAT, true>), dim3(split + grid_for(d2->n_local)), dim3(256),
+                           0, s, *d, *d2, split, pay);
+      else
+        hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT, true>), dim3(split), dim3(256), 0, s, *d, cut->blk0, pay);
       return;
     }
   }
-  hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT>), dim3(split), dim3(256), 0, s, *d);
+  if constexpr (MODEL != SIM_MORTALITY) {
+    if (d2) {
+      hipLaunchKernelGGL((k_sim_scan_pair<Real, AL, MODEL, STAT>), dim3(split + grid_for(d2->n_local)), dim3(256), 0, s,
+                         *d, *d2, split, pay);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_sim_scan<Real, AL, MODEL, STAT>), dim3(split), dim3(256), 0, s, *d, cut ? cut->blk0 : 0, pay);
 }
 
 // GBM scans with a running path statistic (SimDesc.path_stat, validated by rph_simulate)
 template <typename Real, bool AL, int MODEL>
-static int launch_scan_stat(const SimDesc* d, const SimDesc* d2, hipStream_t s) {
+static int launch_scan_stat(const SimDesc* d, const SimDesc* d2, hipStream_t s, const ScanCut* cut) {
   switch (d->path_stat) {
-    case STAT_MEAN: launch_scan_kernel<Real, AL, MODEL, STAT_MEAN>(d, d2, s); break;
-    case STAT_GEOMEAN: launch_scan_kernel<Real, AL, SIM_GBM_LOG, STAT_GEOMEAN>(d, d2, s); break;
-    case STAT_MAX: launch_scan_kernel<Real, AL, MODEL, STAT_MAX>(d, d2, s); break;
-    case STAT_MIN: launch_scan_kernel<Real, AL, MODEL, STAT_MIN>(d, d2, s); break;
+    case STAT_MEAN: launch_scan_kernel<Real, AL, MODEL, STAT_MEAN>(d, d2, s, cut); break;
+    case STAT_GEOMEAN: launch_scan_kernel<Real, AL, SIM_GBM_LOG, STAT_GEOMEAN>(d, d2, s, cut); break;
+    case STAT_MAX: launch_scan_kernel<Real, AL, MODEL, STAT_MAX>(d, d2, s, cut); break;
+    case STAT_MIN: launch_scan_kernel<Real, AL, MODEL, STAT_MIN>(d, d2, s, cut); break;
     default: return -1;
   }
   return (int)hipGetLastError();
 }
 
 template <typename Real, bool AL>
-static int launch_scan(const SimDesc* d, hipStream_t s, const SimDesc* d2 = nullptr) {
+static int launch_scan(const SimDesc* d, hipStream_t s, const SimDesc* d2 = nullptr, const ScanCut* cut = nullptr) {
   if (d->path_stat != STAT_NONE)
-    return d->model == SIM_GBM_LOG ? launch_scan_stat<Real, AL, SIM_GBM_LOG>(d, d2, s)
-                                   : launch_scan_stat<Real, AL, SIM_GBM_ARITH>(d, d2, s);
+    return d->model == SIM_GBM_LOG ? launch_scan_stat<Real, AL, SIM_GBM_LOG>(d, d2, s, cut)
+                                   : launch_scan_stat<Real, AL, SIM_GBM_ARITH>(d, d2, s, cut);
   switch (d->model) {
-    case SIM_GBM_ARITH: launch_scan_kernel<Real, AL, SIM_GBM_ARITH>(d, d2, s); break;
-    case SIM_GBM_LOG: launch_scan_kernel<Real, AL, SIM_GBM_LOG>(d, d2, s); break;
-    case SIM_SV_REF: launch_scan_kernel<Real, AL, SIM_SV_REF>(d, d2, s); break;
-    case SIM_HESTON: launch_scan_kernel<Real, AL, SIM_HESTON>(d, d2, s); break;
+    case SIM_GBM_ARITH: launch_scan_kernel<Real, AL, SIM_GBM_ARITH>(d, d2, s, cut); break;
+    case SIM_GBM_LOG: launch_scan_kernel<Real, AL, SIM_GBM_LOG>(d, d2, s, cut); break;
+    case SIM_SV_REF: launch_scan_kernel<Real, AL, SIM_SV_REF>(d, d2, s, cut); break;
+    case SIM_HESTON: launch_scan_kernel<Real, AL, SIM_HESTON>(d, d2, s, cut); break;
     case SIM_MORTALITY: launch_scan_kernel<Real, AL, SIM_MORTALITY>(d, nullptr, s); break;
     default: return -1;
   }
@@ -433,6 +343,66 @@ extern "C" int rph_simulate_pair(const SimDesc* a, const SimDesc* b, int* merged
   if (merged) *merged = 1;
   if (a->fp64) return aligned ? launch_scan<double, true>(a, s, b) : launch_scan<double, false>(a, s, b);
   return aligned ? launch_scan<float, true>(a, s, b) : launch_scan<float, false>(a, s, b);
+}
+
+// ---------------------------------------------------------------------------
+// The sim ride (SimRideDesc): the head launch, the slice schedule of the
+// riders, and the plain launch of the blocks nobody has simulated yet.
+// ---------------------------------------------------------------------------
+namespace rph {
+int validate_sim_ride(const SimRideDesc* r, const char* who) {
+  if (!r) return rph_report(who, "null SimRideDesc");
+  const SimDesc* d = &r->sim;
+  if (int rc = validate_sim(d, who)) return rc;
+  if ((d->model != SIM_GBM_ARITH && d->model != SIM_GBM_LOG && d->model != SIM_HESTON) || d->path_stat != STAT_NONE)
+    return rph_report(who, "sim ride: GBM or Heston scans without a path statistic");
+  if (d->fp64 || d->map_blk != 0 || !sim_aligned(d)) return rph_report(who, "sim ride: fp32, contiguous aligned paths");
+  if (!d->out || !d->final_out || !r->pay_out) return rph_report(who, "sim ride: null out / final_out / pay_out");
+  if (r->pay_kind != 1 && r->pay_kind != 2) return rph_report(who, "sim ride: payoff kinds 1 (call) / 2 (put)");
+  if (r->b0 < 0 || r->b1 != grid_for(d->n_local) || r->b0 > r->b1 || r->per_rider < 1)
+    return rph_report(who, "sim ride: bad block range / blocks per rider");
+  return 0;
+}
+}  // namespace rph
+
+// Slice k of the riders' schedule: blocks [*start, *start + *count) of [b0, b1)
+// go to solve launch k (count 0: none left); rider r of `riders` scans the
+// blocks *start + r + j * riders below *start + *count, j < per_rider.
+// Returns the first block no slice up to k covers.
+extern "C" int rph_sim_ride_slice(int b0, int b1, int riders, int per_rider, int k, int* start, int* count) {
+  const SimRideSlice sl = sim_ride_slice(b0, b1, riders, per_rider, k);
+  if (start) *start = sl.start;
+  if (count) *count = sl.count;
+  return sl.start + sl.count;
+}
+
+static SimPay ride_pay(const SimRideDesc* r) { return SimPay{r->pay_out, r->pay_out2, r->strike, r->pay_kind}; }
+
+// Blocks [0, b0) of the ride's scan with their payoff, and the whole scan g
+// (the LM Gram subsample; may be null) beside them: one launch.
+extern "C" int rph_sim_ride_head(const SimRideDesc* r, const SimDesc* g, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = validate_sim_ride(r, "rph_sim_ride_head")) return rc;
+  const SimDesc* a = &r->sim;
+  if (g) {
+    if (int rc = validate_sim(g, "rph_sim_ride_head")) return rc;
+    if (g->model != a->model || g->fp64 || g->path_stat != a->path_stat || !sim_aligned(g))
+      return rph_report("rph_sim_ride_head", "the second scan must select the same kernel");
+  }
+  if (r->b0 == 0 && !g) return 0;
+  const ScanCut cut{0, r->b0, ride_pay(r)};
+  if (r->b0 == 0) return launch_scan<float, true>(g, s);
+  return launch_scan<float, true>(a, s, g, &cut);
+}
+
+// Blocks [from, b1) of the ride's scan with their payoff in one plain launch
+// (from >= b1: nothing).
+extern "C" int rph_sim_ride_rest(const SimRideDesc* r, int from, void* stream) {
+  if (int rc = validate_sim_ride(r, "rph_sim_ride_rest")) return rc;
+  if (from < r->b0) return rph_report("rph_sim_ride_rest", "block below the ride's range");
+  if (from >= r->b1) return 0;
+  const ScanCut cut{from, r->b1 - from, ride_pay(r)};
+  return launch_scan<float, true>(&r->sim, (hipStream_t)stream, nullptr, &cut);
 }
 
 extern "C" int rph_payoff(int kind, int n, int na, const float* s, const float* nfrac, float strike,

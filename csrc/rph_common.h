@@ -218,6 +218,26 @@ RPH_INLINE uint32_t sobol_point(const uint32_t* __restrict__ sv_d, uint32_t shif
   return x;
 }
 
+// The aligned fold with no memory round trip per bit: the dimension's 32
+// direction numbers are fetched whole (a wave-uniform address: wide scalar
+// loads, one round trip) and folded by bit masks on registers - the
+// wave-uniform bits (hu = gray >> 6 of the wave, read once per path) on the
+// scalar unit, the six lane bits on the vector unit.  XOR is associative: the
+// same 30-bit integer as sobol_point<true> for every index below 2^30.  For
+// the scans that run at low occupancy (a split scan's head and riders), where
+// nothing hides the per-bit loads of sobol_point.
+RPH_INLINE uint32_t sobol_point_wide(const uint32_t* __restrict__ sv_d, uint32_t shift_d, uint32_t gray, uint32_t hu) {
+  uint32_t r[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) r[k] = sv_d[k];
+  uint32_t x = shift_d;
+#pragma unroll
+  for (int k = 0; k < 26; ++k) x ^= r[6 + k] & (0u - ((hu >> k) & 1u));
+#pragma unroll
+  for (int k = 0; k < 6; ++k) x ^= r[k] & (0u - ((gray >> k) & 1u));
+  return x;
+}
+
 RPH_INLINE uint32_t gray_code(uint64_t i) { return (uint32_t)(i ^ (i >> 1)); }
 
 // LeakyReLU (Keras-2 default alpha=0.3)

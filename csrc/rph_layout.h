@@ -59,6 +59,9 @@ namespace rph {
 
 #define RPH_FIELDS_SelfTargetDesc(X, T) X(T, st_feat) X(T, st_wts) X(T, st_out) X(T, st_fmu) X(T, st_fisd)
 
+#define RPH_FIELDS_SimRideDesc(X, T) \
+  X(T, sim) X(T, pay_out) X(T, pay_out2) X(T, strike) X(T, pay_kind) X(T, b0) X(T, b1) X(T, per_rider) X(T, pad_ride)
+
 #define RPH_DESCRIPTORS(X) \
   X(TrainDesc) X(EvalDesc) X(PnlFinishDesc) X(PnlDesc) X(LmDpDesc) X(LmDesc) X(SimDesc)
 // Descriptors of later kernels, in a table of their own (rph_layout_fields_ext;
@@ -66,6 +69,8 @@ namespace rph {
 #define RPH_DESCRIPTORS_EXT(X) X(OosDesc)
 // ... and of the eval ride (rph_layout_fields_ride; native.py DESCRIPTORS_RIDE)
 #define RPH_DESCRIPTORS_RIDE(X) X(SelfTargetDesc)
+// ... and of the sim ride (rph_layout_fields_sim; native.py DESCRIPTORS_SIM)
+#define RPH_DESCRIPTORS_SIM(X) X(SimRideDesc)
 
 struct FieldRow {
   const char* strct;
@@ -78,6 +83,7 @@ struct FieldRow {
 constexpr FieldRow kFieldRows[] = {RPH_DESCRIPTORS(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsExt[] = {RPH_DESCRIPTORS_EXT(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsRide[] = {RPH_DESCRIPTORS_RIDE(RPH_STRUCT_ROWS)};
+constexpr FieldRow kFieldRowsSim[] = {RPH_DESCRIPTORS_SIM(RPH_STRUCT_ROWS)};
 
 // The listed fields of `strct` start at 0, follow each other with no gap and
 // end at `size`: with no implicit padding in the struct, none is left out.
@@ -102,9 +108,11 @@ constexpr bool layout_covers(const FieldRow (&rows)[N], const char* strct, size_
 #define RPH_STRUCT_COVERED(T) RPH_STRUCT_COVERED_IN(kFieldRows, T)
 #define RPH_STRUCT_COVERED_EXT(T) RPH_STRUCT_COVERED_IN(kFieldRowsExt, T)
 #define RPH_STRUCT_COVERED_RIDE(T) RPH_STRUCT_COVERED_IN(kFieldRowsRide, T)
+#define RPH_STRUCT_COVERED_SIM(T) RPH_STRUCT_COVERED_IN(kFieldRowsSim, T)
 RPH_DESCRIPTORS(RPH_STRUCT_COVERED)
 RPH_DESCRIPTORS_EXT(RPH_STRUCT_COVERED_EXT)
 RPH_DESCRIPTORS_RIDE(RPH_STRUCT_COVERED_RIDE)
+RPH_DESCRIPTORS_SIM(RPH_STRUCT_COVERED_SIM)
 
 // Constants, by their names in rphedge/ops/layout.py.
 struct ConstRow {

@@ -544,6 +544,35 @@ struct OosDesc {
   int nin, h, nout, head;
 };
 
+// The run's scan split over the launches of a first date's multi-start
+// exploration (the sim ride).  The exploration reads only the first paths of
+// the shard, so a head launch simulates the 256-path blocks [0, b0) (with the
+// LM Gram subsample, as k_sim_scan_pair does) and the blocks [b0, b1) are
+// simulated by rider workgroups of the exploration's solve launches
+// (k_lm_solve_sim), on the CUs its few solve workgroups leave idle; what the
+// solves cannot carry goes out as one k_sim_scan launch behind the last of
+// them.  Every block runs sim_scan_block on `sim` exactly as in a launch of its
+// own and then writes its paths' payoff (the k_payoff expression on the float
+// the scan stored as final_out) to pay_out and pay_out2.
+//   sim: SIM_GBM_ARITH | SIM_GBM_LOG | SIM_HESTON without a path statistic,
+//     fp32, contiguous aligned indices (map_blk = 0), final_out set: the scans
+//     that have a rider (GBM under the one-input nets, Heston under 2-8-8-2:
+//     rph_lm_has_sim).
+//   pay_kind: the k_payoff kinds 1 (call) / 2 (put) on the terminal price.
+//   slice k (solve launch k = 0, 1, ...) is blocks [b0 + k * riders * per_rider,
+//     + riders * per_rider) cut at b1; rider r of `riders` takes the blocks
+//     start + r + j * riders, j < per_rider (sim_ride_slice).
+struct SimRideDesc {
+  SimDesc sim;
+  float* pay_out;                // payoff [n_local]
+  float* pay_out2;               // second copy of the payoff [n_local] (may be null)
+  float strike;
+  int pay_kind;
+  int b0, b1;                    // blocks still to simulate after the head launch
+  int per_rider;                 // blocks per rider per solve launch (>= 1)
+  int pad_ride;
+};
+
 enum HestonScheme : int { HESTON_EULER = 0, HESTON_QE = 1 };
 
 // Running statistic of the fine-grid GBM path at fine point j >= 1 (S_0 at

@@ -63,6 +63,11 @@ extern "C" int rph_layout_fields_ride(const FieldRow** rows) {
   return (int)(sizeof(kFieldRowsRide) / sizeof(kFieldRowsRide[0]));
 }
 
+extern "C" int rph_layout_fields_sim(const FieldRow** rows) {
+  *rows = kFieldRowsSim;
+  return (int)(sizeof(kFieldRowsSim) / sizeof(kFieldRowsSim[0]));
+}
+
 extern "C" int rph_layout_consts(const ConstRow** rows) {
   *rows = kConstRows;
   return (int)(sizeof(kConstRows) / sizeof(kConstRows[0]));

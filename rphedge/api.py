@@ -93,6 +93,10 @@ class HedgeRun:
         self.offset, self.n_local = D.shard(self.n_total, dist_info.world, dist_info.rank)
         self.timer = PhaseTimer(enabled=True, device=self.device)
         self.path_stat = None  # running path statistic of a path-dependent payoff (set by _kind)
+        # sim ride: the SimRideDesc of an in-place re-simulation whose head launch
+        # is enqueued and whose other blocks the next enqueue() hands to the first
+        # date's fit (None: the paths are whole; flush_sim_ride)
+        self.sim_ride = None
         self.kind = self._kind()
         self.exercise = self._exercise()
         self.spec = self._spec()
@@ -190,6 +194,7 @@ class HedgeRun:
         simulation can be captured into the run's hipGraph.  LM fits also get
         the global Gram subsample simulated on this rank (:meth:`gram_paths`)."""
         c = self.cfg
+        self.flush_sim_ride()  # (a split re-simulation nobody finished: finish it before its buffers are rewritten)
         vt_out = self.v_terminal if into is not None else None
         tr = c.train
         lm = str(tr.optimizer).lower() == "lm"
@@ -203,10 +208,19 @@ class HedgeRun:
                 ns, blk, stride = gram_subsample(self.n_total, tr.lm_gram_paths)
                 self.gpaths = self._simulate_paths(ns, 0, (blk, stride), self.gpaths if into is not None else None,
                                                    defer=pair)
-            if pair is not None:
+            ride = self._sim_ride_desc(*pair) if (into is not None and pair is not None and len(pair) == 2) else None
+            if ride is not None:
+                # sim ride: the blocks the first date's exploration reads, the Gram
+                # subsample and that prefix's payoff in one launch; the other blocks
+                # and their payoff ride in the exploration's solves (enqueue)
                 from .ops import native
-                native.simulate_pair(pair[0], pair[1], self.stream)
-            v_t = self._payoff(p, vt_out)
+                native.sim_ride_head(ride, pair[1], self.stream)
+                self.sim_ride, v_t = ride, vt_out
+            else:
+                if pair is not None:
+                    from .ops import native
+                    native.simulate_pair(pair[0], pair[1], self.stream)
+                v_t = self._payoff(p, vt_out)
             if lm:
                 if self._q_lm():
                     # pinball LM fits: the subsample's own terminal values (its
@@ -221,6 +235,55 @@ class HedgeRun:
                     self.xpaths = (xp, xv)
         self.paths, self.v_terminal = p, v_t
         return p, v_t
+
+    def _sim_ride_desc(self, d, g=None):
+        """The SimRideDesc of an in-place re-simulation with the scan ``d`` of the
+        run's paths (``g``: the Gram subsample's scan, which the head launch
+        carries and which must select the same kernel), or None where the run keeps the plain sequence (scan,
+        payoff, copy): it needs a built induction whose first date's fit can
+        carry the scan (BackwardInduction.sim_ride_ok), fp32 aligned contiguous
+        paths, a call / put payoff of the path's own terminal values and more
+        blocks than the exploration reads.  Launches nothing."""
+        from .ops import native
+
+        c, ind = self.cfg, self.induction
+        if ind is None or getattr(self, "v_terminal", None) is None or self.kind != "european" or self.backend_kind != "hip":
+            return None
+        if d.fp64 or d.map_blk != 0 or d.n_local % 256 != 0 or d.path_offset % 64 != 0 or not d.final_out:
+            return None
+        if self.path_stat is not None or d.path_stat:
+            return None  # (scans with a path statistic have no rider)
+        kind = {"call": 1, "put": 2}.get(c.option_type.lower())
+        if kind is None or not ind.sim_ride_ok(d.model, d.path_stat):
+            return None
+        if g is not None and (g.model != d.model or g.fp64 or g.path_stat != d.path_stat or g.n_local % 256 != 0
+                              or g.path_offset % 64 != 0 or (g.map_blk and (g.map_blk % 64 or g.map_stride % 64))):
+            return None  # (another scan kernel: native.simulate_pair launches the two apart)
+        # a rider walks a whole block beside one solve: only scans short enough to end with it (HipBackend.sim_ride_steps)
+        tables = 2 if d.model in (L.SIM_SV_REF, L.SIM_HESTON) else 1
+        if (int(d.n_fine) - 1) * tables > self.backend.sim_ride_steps():
+            return None
+        fcfg = ind._fcfg(True, L.LOSS_MSE, ind.paths.n_coarse - 2)
+        b0, b1 = -(-int(self.backend.lm_explore_paths(fcfg)) // 256), int(d.n_local) // 256
+        if b0 >= b1:
+            return None
+        r = native.SimRideDesc()
+        r.sim = type(d).from_buffer_copy(d)
+        r.pay_out, r.pay_out2 = self.v_terminal.data_ptr(), ind.values[-1].data_ptr()
+        r.strike, r.pay_kind = float(c.K / c.Y), int(kind)
+        r.b0, r.b1 = b0, b1
+        r.per_rider = int(self.backend.sim_ride_blocks())
+        return r
+
+    def flush_sim_ride(self):
+        """Finish a split re-simulation that no fit has carried: the blocks past
+        the head launch and their payoff go out as one plain launch, so whoever
+        reads the paths next (another simulation, ``collect``, the
+        out-of-sample test, a resume) finds them whole."""
+        ride, self.sim_ride = self.sim_ride, None
+        if ride is not None:
+            from .ops import native
+            native.sim_ride_rest(ride, None, self.stream)
 
     def _q_lm(self) -> bool:
         """Both networks with the pinball fit on Levenberg-Marquardt."""
@@ -413,7 +476,8 @@ class HedgeRun:
                            lm_lam_down=float(tr.lm_lam_down), lm_out_fix=bool(tr.lm_out_fix),
                            lm_out_mu=float(tr.lm_out_mu), lm_out_tr=float(getattr(tr, "lm_out_tr", 0.0)),
                            lm_ridge=float(getattr(tr, "lm_ridge", 1e-10)),
-                           lm_diag_floor=float(tr.lm_diag_floor), eval_ride=bool(getattr(tr, "eval_ride", True)))
+                           lm_diag_floor=float(tr.lm_diag_floor), eval_ride=bool(getattr(tr, "eval_ride", True)),
+                           sim_ride=bool(getattr(tr, "sim_ride", True)))
         if int(tr.variant) >= 0:
             tcfg.variant = int(tr.variant)
         kw = {}
@@ -485,7 +549,11 @@ class HedgeRun:
         ind = self.induction
         if resimulate:
             self.simulate()  # same buffers are re-created; only used outside capture
-        ind.values[-1].copy_(self.v_terminal)
+        # (a pending sim ride: its kernels write values[-1] beside v_terminal, and
+        # the first date's fit finishes the scan)
+        ride, self.sim_ride = self.sim_ride, None
+        if ride is None:
+            ind.values[-1].copy_(self.v_terminal)
         if ind.gvalues is not None:
             ind.gvalues[-1].copy_(ind.g_terminal)
         ind.w_mse.copy_(ind.w_init)
@@ -495,7 +563,7 @@ class HedgeRun:
                 ind.w_q.copy_(ind.w_init)
             ind.opt_q.copy_(ind.opt_init)
         with self.timer.phase("train"):
-            ind.enqueue()
+            ind.enqueue(sim_ride=ride)
 
     def capture(self, include_simulation: bool = True):
         """Capture simulation + full backward induction into ONE hipGraph."""
@@ -556,6 +624,7 @@ class HedgeRun:
 
         if self.induction is None:
             self.build()
+        self.flush_sim_ride()
         ind = self.induction
         _, spec, w, wq, vals = load_date(out_dir, date)
         assert spec.nparams == self.spec.nparams, "saved network shape differs from this configuration"
@@ -633,11 +702,13 @@ class HedgeRun:
         fitted V0.  Valid after ``run()``, ``replay()`` or ``resume()``."""
         from .oos import out_of_sample
 
+        self.flush_sim_ride()
         return out_of_sample(self, paths_log2=paths_log2, seed=seed, offset=offset, stress=stress, fused=fused,
                              keep_pnl=keep_pnl, keep_paths=keep_paths)
 
     def collect(self) -> RunResult:
         c, w = self.cfg, self.di.world
+        self.flush_sim_ride()
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         for mb in (getattr(self, "mailbox", None), getattr(self, "lm_mailbox", None)):

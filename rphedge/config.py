@@ -141,6 +141,7 @@ class TrainingParams:
     lm_lam0_first: float = 0.0       # first date's initial LM damping (0: lm_lam0)
     lm_diag_floor: float = 0.0       # LM damping diagonal floor, relative to mean diag 2G (0: Marquardt scaling)
     eval_ride: bool = True           # eligible LM runs: a date's eval rides in the next fit's first solve launch
+    sim_ride: bool = True            # eligible LM runs: the re-simulated paths ride under the first date's exploration solves
                                      # (False: every eval a launch of its own; same results bit for bit)
     mean_refit: bool = True          # after each Adam MSE fit: exact refit of the bond holding's bias (the
                                      # residual mean over all paths -> 0; no mean error drifts into V0)

@@ -393,13 +393,29 @@ class BackwardInduction:
         else:
             self.eval_gram_values(date, with_target=False)
 
-    def enqueue(self, start: int | None = None):
+    def sim_ride_ok(self, model: int, path_stat: int) -> bool:
+        """Whether the first date's fit of this run can carry the scan of the
+        run's paths under its exploration's solves (HipBackend.sim_ride_ok):
+        one network, one rank, a first date with a multi-start exploration on
+        the shard's own prefix, no per-path reports."""
+        c, be = self.cfg, self.backend
+        return bool(hasattr(be, "sim_ride_ok") and c.optimizer == "lm" and not c.q99 and self.world == 1
+                    and (c.lm_starts > 1 or c.lm_explore_one) and not c.keep_paths and self.explore_paths is None
+                    and be.sim_ride_ok(self._fcfg(True, L.LOSS_MSE, self.paths.n_coarse - 2), model, path_stat))
+
+    def enqueue(self, start: int | None = None, sim_ride=None):
         """Enqueue dates ``start, start-1, ..., 0`` (default: all, from n-2).
         Resume restarts at ``start = i-1`` after loading the
-        weights and ``values[i]`` of a saved date i."""
+        weights and ``values[i]`` of a saved date i.
+
+        ``sim_ride`` (a SimRideDesc whose head launch is enqueued; only where
+        :meth:`sim_ride_ok` and from the last date): the first fit's exploration
+        simulates the remaining path blocks in its solve launches."""
         c, be = self.cfg, self.backend
         nc = self.paths.n_coarse
         start = nc - 2 if start is None else int(start)
+        if sim_ride is not None and start != nc - 2:
+            raise ValueError("a path scan rides in the first date's fit only")
         self.ran = list(range(start, -1, -1))
         # the P&L needs every date: a resumed run (start below the last date) reports none
         self.pnl_done = start == nc - 2
@@ -453,7 +469,8 @@ class BackwardInduction:
                 self.eval_rides += 1
             else:
                 be.fit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE, t),
-                       seed=fit_seed(c.seed, t, 0), poll_every=c.poll_every)
+                       seed=fit_seed(c.seed, t, 0), poll_every=c.poll_every,
+                       **(dict(sim_ride=sim_ride) if first and sim_ride is not None else {}))
             if c.mean_refit and c.optimizer != "lm":
                 be.bias_refit(self.w_mse, self.opt_mse, f_m, data, self._fcfg(first, L.LOSS_MSE))
             hold_out = [self.holdings[t, k] for k in range(self.spec.nhold)] if self.holdings is not None else None

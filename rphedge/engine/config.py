@@ -157,6 +157,10 @@ class TrainConfig:
     # evaluates its own target; False forces the sequence fit, eval, fit, ...
     # with every eval a launch of its own (same results bit for bit)
     eval_ride: bool = True
+    # first date of an eligible LM run (HipBackend.sim_ride_ok): the in-place
+    # re-simulation launches only the path blocks the exploration reads; the
+    # others ride in the exploration's solve launches (k_lm_solve_sim)
+    sim_ride: bool = True
     expose_packet: bool = False    # lagged fits: the finalize kernel writes the last step's summed (and
                                    # data-parallel exchanged) gradient packet to HipBackend.grad (tests)
     # optimizer-step schedule on the GPU:

@@ -140,7 +140,8 @@ class HipBackend(StateBlocks):
         d.loss = int(loss)
         return d
 
-    def fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, poll_every: int = 0, ride=None):
+    def fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, seed: int, poll_every: int = 0, ride=None,
+            sim_ride=None):
         """Enqueue a full Keras ``fit`` (epochs x steps).  With ``poll_every``>0 the
         host checks the device early-stop flag every that many epochs and stops
         enqueueing; otherwise everything is asynchronous (graph-capturable) and
@@ -152,9 +153,9 @@ class HipBackend(StateBlocks):
         and the eval runs as extra workgroups of the first solve's launch."""
         assert len(data.feats) == self.spec.nin and len(data.prices_next) == self.spec.nhold - 1
         if fcfg.optimizer == "lm":
-            return self._lm_fit(wts, opt, fit, data, fcfg, ride)
-        if ride is not None:
-            raise ValueError("an eval rides in Levenberg-Marquardt fits only")
+            return self._lm_fit(wts, opt, fit, data, fcfg, ride, sim_ride)
+        if ride is not None or sim_ride is not None:
+            raise ValueError("an eval or a path scan rides in Levenberg-Marquardt fits only")
         d = self._train_desc(wts, opt, fit, data, fcfg, seed, self._lr(fcfg))
         n, S = self.native, self.steps_per_epoch
         mode = self.step_mode(poll_every)
@@ -356,6 +357,52 @@ class HipBackend(StateBlocks):
                     and int(fcfg.epochs) >= 1 and fcfg.lm_renorm is None
                     and not (int(fcfg.lm_starts) >= 1 and int(fcfg.lm_explore_passes) > 0))
 
+    def sim_riders(self, K: int) -> int:
+        """Rider workgroups of k_lm_solve_sim under the solves of ``K``
+        exploration instances: one per CU that the ``K x LM_SPEC`` solve
+        workgroups leave free.  :meth:`eval_riders` fills every slot (two per CU
+        where two LDS images fit) under ONE main solve; here 21 latency-bound
+        solves in a row each carry riders, and a rider that shares a CU with a
+        solve workgroup slows that solve: euro30 with 448 / 384 / 320 / 256 /
+        192 riders: 4.679 / 4.668 / 4.663 / 4.674 / 4.649 ms against 4.717
+        without the ride (profiles/sim_ride/sweep.txt)."""
+        cus = 256
+        if self.device.type == "cuda":
+            cus = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
+        return max(1, min(4096, _env("SIM_RIDERS", cus - int(K) * L.LM_SPEC)))
+
+    def sim_ride_steps(self) -> int:
+        """The longest scan, in Sobol points per path (fine steps x tables),
+        whose blocks ride under the exploration's solves.  A rider runs at one
+        wave per SIMD, where a block costs its per-step latency times its steps
+        whatever else the CU does, and a solve launch ends with its slowest
+        rider.  Derived from two measured times: an exploration solve takes
+        22 us and a block of 30 points 20 us (0.67 us per point: the head
+        launch of euro30, profiles/sim_ride/phases_commit.txt), so 22 / 0.67 =
+        32 points still end with the solve.  Longer scans stretch every solve
+        they ride in (600 points, heston30: 8.0 -> 18.4 ms per replay; 252
+        points, euro252: 50.1 -> 52.8 ms; profiles/sim_ride/long_scans_riding.txt)
+        and keep the plain scan.  ``RPH_SIM_RIDE_STEPS`` overrides (tests)."""
+        return _env("SIM_RIDE_STEPS", 32)
+
+    def sim_ride_blocks(self) -> int:
+        """Blocks per rider per solve launch: one (two in a row outlast the
+        solve: 4.723 against 4.679 ms, profiles/sim_ride/sweep.txt).
+        ``RPH_SIM_RIDE_BLOCKS`` overrides (A/B)."""
+        return max(1, _env("SIM_RIDE_BLOCKS", 1))
+
+    def sim_ride_ok(self, fcfg: FitConfig, model: int | None = None, path_stat: int = 0) -> bool:
+        """Whether a first-date fit with ``fcfg`` can carry the run's path scan
+        under its exploration's solves (:meth:`fit` ``sim_ride``): the switch is
+        on, one rank, an MSE LM fit launched whole with a multi-start
+        exploration on this rank's own path prefix, and (``model`` given) a
+        rider for that scan under this net's solve.  The caller adds what it
+        alone knows: an in-place re-simulation of one network's run."""
+        return bool(self.tcfg.sim_ride and _env("SIM_RIDE", 1) and self.world == 1 and not self.tcfg.lm_split
+                    and fcfg.optimizer == "lm" and int(fcfg.loss) == L.LOSS_MSE and self.lm_supported()
+                    and int(fcfg.lm_starts) >= 1 and int(fcfg.lm_explore_passes) > 0 and fcfg.lm_explore_data is None
+                    and (model is None or self.native.lm_has_sim(*self.shape, int(model), int(path_stat))))
+
     def _lm_self_target(self, d, ride):
         """The SelfTargetDesc of pass 0 of a fit (TrainDesc ``d``) that carries the eval ``ride``."""
         st = self.native.SelfTargetDesc()
@@ -397,7 +444,7 @@ class HipBackend(StateBlocks):
             return d, lm, self._lm_self_target(d, ride)
         return d, lm
 
-    def _lm_fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, ride=None):
+    def _lm_fit(self, wts, opt, fit, data: DateData, fcfg: FitConfig, ride=None, sim_ride=None):
         """Enqueue a full-batch Levenberg-Marquardt fit (MSE): ``fcfg.epochs``
         trial points after the start point, 3 launches each (pass, reduce,
         solve), graph-capturable; data parallel: the gradient region [g |
@@ -405,8 +452,10 @@ class HipBackend(StateBlocks):
         (every rank builds the same Gram matrix from the simulated global
         subsample; without it the whole reduced block travels)."""
         d, lm, *st = self._lm_prepare(wts, opt, fit, data, fcfg, ride)
+        if sim_ride is not None and not self.sim_ride_ok(fcfg, sim_ride.sim.model, sim_ride.sim.path_stat):
+            raise ValueError("this fit cannot carry a path scan (sim_ride_ok)")
         if int(fcfg.lm_starts) >= 1 and int(fcfg.lm_explore_passes) > 0:
-            self._lm_explore(d, fcfg)
+            self._lm_explore(d, fcfg, sim_ride)
         self._lm_launch(d, lm, self._lm_buffers(fcfg.loss)["red"],
                         (self.world <= 1 or lm.dp_fused) and not self.tcfg.lm_split, not self._lm_same_gram, ride, st[0] if st else None)
 
@@ -489,7 +538,7 @@ class HipBackend(StateBlocks):
         d.inv_batch = 1.0 / float(nsub)
         return d, x["desc"], x
 
-    def _lm_explore(self, d_main, fcfg: FitConfig):
+    def _lm_explore(self, d_main, fcfg: FitConfig, sim_ride=None):
         """Multi-start exploration of a first date (graph-capturable): K
         independent LM fits in ONE launch per kernel (grid y = instance) on the
         global path prefix (FitConfig.lm_explore_data, or this rank's shard
@@ -515,7 +564,14 @@ class HipBackend(StateBlocks):
                 x["w0"].copy_(w0)
             x["w0_rows"] = rows.tobytes()
         n, main_state = self.native, self._lm_buffers()["state"]
-        n.lm_fit(d, lm, x["red"], self.stream)
+        if sim_ride is not None:
+            # (the exploration reads the blocks the head launch simulated: the
+            # others ride in its solve launches, all of them enqueued on return)
+            if int(sim_ride.b0) * 256 < int(d.n_local):
+                raise ValueError("sim ride: the head launch does not cover the exploration's paths")
+            n.lm_fit_sim(d, lm, x["red"], sim_ride, self.sim_riders(K), self.stream)
+        else:
+            n.lm_fit(d, lm, x["red"], self.stream)
         n.lm_select(d, lm, x["sel"], main_state, 1, 0, P, 0, self.stream)
         n.lm_select(d, lm, x["sel"], main_state, 1, 0, P, 1, self.stream)
         self.lm_explore_last = x

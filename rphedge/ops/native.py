@@ -166,12 +166,25 @@ class OosDesc(C.Structure):
     ]
 
 
+class SimRideDesc(C.Structure):
+    """The run's scan split over the solve launches of a first date's
+    exploration (csrc/rph_types.h): ``sim`` is the run's scan, blocks
+    ``[b0, b1)`` of 256 paths are still to simulate after the head launch."""
+
+    _fields_ = [
+        ("sim", SimDesc), ("pay_out", VP), ("pay_out2", VP), ("strike", C.c_float), ("pay_kind", C.c_int),
+        ("b0", C.c_int), ("b1", C.c_int), ("per_rider", C.c_int), ("pad_ride", C.c_int),
+    ]
+
+
 DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, SimDesc)
 # descriptors of the native library's second field table (csrc/rph_layout.h
 # RPH_DESCRIPTORS_EXT, rph_layout_fields_ext): checked by name at load like the first
 DESCRIPTORS_EXT = (OosDesc,)
 # ... and of its third (RPH_DESCRIPTORS_RIDE, rph_layout_fields_ride): the eval ride
 DESCRIPTORS_RIDE = (SelfTargetDesc,)
+# ... and its fourth (RPH_DESCRIPTORS_SIM, rph_layout_fields_sim): the sim ride
+DESCRIPTORS_SIM = (SimRideDesc,)
 
 # upper-case ints of layout.py that the native table does not hold (Python only)
 PYTHON_ONLY: tuple[str, ...] = ()
@@ -208,6 +221,13 @@ def native_layout_ride(lib) -> list[tuple[str, str, int, int]]:
     return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
 
 
+def native_layout_sim(lib) -> list[tuple[str, str, int, int]]:
+    """The library's fourth field table: the rows of :data:`DESCRIPTORS_SIM`."""
+    fr = C.POINTER(_FieldRow)()
+    nf = lib.rph_layout_fields_sim(C.byref(fr))
+    return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
+
+
 def layout_mismatches(fields, consts, classes=DESCRIPTORS, layout=L) -> list[str]:
     """Every difference between the native tables (:func:`native_layout`) and
     the Python mirrors: the ctypes ``classes`` field by field (offset and size
@@ -239,6 +259,14 @@ def _bind(lib):
         "rph_layout_consts": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
         "rph_layout_fields_ext": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_fields_ride": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_layout_fields_sim": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_sim_ride_slice": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2),
+        "rph_sim_ride_head": (C.c_int, [C.POINTER(SimRideDesc), C.POINTER(SimDesc), VP]),
+        "rph_sim_ride_rest": (C.c_int, [C.POINTER(SimRideDesc), C.c_int, VP]),
+        "rph_lm_has_sim": (C.c_int, [C.c_int] * 6),
+        "rph_lm_solve_sim": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.c_int, C.POINTER(SimRideDesc),
+                                       C.c_int, C.c_int, VP]),
+        "rph_lm_fit_sim": (C.c_int, [C.POINTER(TrainDesc), C.POINTER(LmDesc), VP, C.POINTER(SimRideDesc), C.c_int, VP]),
         "rph_oos": (C.c_int, [C.POINTER(OosDesc), VP]),
         "rph_oos_check": (C.c_int, [C.POINTER(OosDesc)]),
         "rph_oos_max_wgs": (C.c_int, [C.POINTER(C.c_int)]),
@@ -322,8 +350,8 @@ def load(required: bool | None = None):
         lib = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         _bind(lib)
         fields, consts = native_layout(lib)
-        bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib), consts,
-                                classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE)
+        bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib) + native_layout_sim(lib),
+                                consts, classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE + DESCRIPTORS_SIM)
         if bad:
             raise RuntimeError("native/Python layout mismatch:\n  " + "\n  ".join(bad))
         _lib = lib
@@ -411,6 +439,50 @@ def simulate_pair(a: SimDesc, b: SimDesc, stream=None) -> bool:
     merged = C.c_int(0)
     _check(lib.rph_simulate_pair(C.byref(a), C.byref(b), C.byref(merged), stream_handle(stream)), "rph_simulate_pair")
     return bool(merged.value)
+
+
+def sim_ride_slice(b0: int, b1: int, riders: int, per_rider: int, k: int) -> tuple[int, int]:
+    """Slice ``k`` of a sim ride's schedule (csrc/sim_scan.h sim_ride_slice): the
+    ``(start, count)`` of the blocks of ``[b0, b1)`` that solve launch ``k``
+    carries; rider ``r`` scans ``start + r + j * riders``, ``j < per_rider``."""
+    lib = load(required=True)
+    start, count = C.c_int(0), C.c_int(0)
+    lib.rph_sim_ride_slice(int(b0), int(b1), int(riders), int(per_rider), int(k), C.byref(start), C.byref(count))
+    return start.value, count.value
+
+
+def sim_ride_head(r: SimRideDesc, g: SimDesc | None, stream=None):
+    """Blocks ``[0, b0)`` of the ride's scan with their payoff and the whole scan ``g`` beside them: one launch."""
+    lib = load(required=True)
+    _check(lib.rph_sim_ride_head(C.byref(r), C.byref(g) if g is not None else None, stream_handle(stream)),
+           "rph_sim_ride_head")
+
+
+def sim_ride_rest(r: SimRideDesc, start: int | None = None, stream=None):
+    """Blocks ``[start, b1)`` (default: from ``b0``) of the ride's scan with their payoff, one plain launch."""
+    lib = load(required=True)
+    _check(lib.rph_sim_ride_rest(C.byref(r), int(r.b0 if start is None else start), stream_handle(stream)),
+           "rph_sim_ride_rest")
+
+
+def lm_has_sim(nin: int, h: int, nout: int, head: int, model: int, path_stat: int) -> bool:
+    """Whether the shape's solve launch has a rider for the scan (csrc/hedge_lm.hip sim_rider_for)."""
+    return bool(load(required=True).rph_lm_has_sim(nin, h, nout, head, int(model), int(path_stat)))
+
+
+def lm_solve_sim(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, pass_: int, r: SimRideDesc, riders: int, k: int,
+                 stream=None):
+    """The solve of ``pass_`` of an exploration with slice ``k`` of the sim ride on ``riders`` riders (k_lm_solve_sim)."""
+    _check(_lib.rph_lm_solve_sim(C.byref(desc), C.byref(lm), ptr(red_new), int(pass_), C.byref(r), int(riders), int(k),
+                                 stream_handle(stream)), "rph_lm_solve_sim")
+
+
+def lm_fit_sim(desc: TrainDesc, lm: LmDesc, red_new: torch.Tensor, r: SimRideDesc, riders: int, stream=None):
+    """:func:`lm_fit` of an exploration whose solves carry the sim ride ``r``;
+    every block of the ride has been enqueued when it returns."""
+    load(required=True)
+    _check(_lib.rph_lm_fit_sim(C.byref(desc), C.byref(lm), ptr(red_new), C.byref(r), int(riders),
+                               stream_handle(stream)), "rph_lm_fit_sim")
 
 
 def train_step(desc: TrainDesc, step: int, epoch: int, stream=None):

@@ -1,4 +1,4 @@
-"""Per-kernel statistics (calls, total / mean / min us, share) from a rocprofv3
+"""Per-kernel statistics (calls, total / mean / min / max us, share) from a rocprofv3
 results database (rocpd sqlite, the default output format) or a
 kernel_stats.csv.  usage: python tools/kstats.py FILE [name-filter]"""
 import collections
@@ -21,16 +21,18 @@ def main():
     fn = sys.argv[1]
     filt = sys.argv[2] if len(sys.argv) > 2 else ""
     if fn.endswith(".csv"):
-        rows = {r["Name"]: (int(r["Calls"]), float(r["TotalDurationNs"]), float(r["AverageNs"]), float(r["MinNs"]))
+        rows = {r["Name"]: (int(r["Calls"]), float(r["TotalDurationNs"]), float(r["AverageNs"]), float(r["MinNs"]),
+                            float(r.get("MaxNs") or "nan"))
                 for r in csv.DictReader(open(fn))}
     else:
-        rows = {k: (len(v), float(sum(v)), sum(v) / len(v), float(min(v))) for k, v in from_db(fn).items()}
+        rows = {k: (len(v), float(sum(v)), sum(v) / len(v), float(min(v)), float(max(v))) for k, v in from_db(fn).items()}
     tot = sum(r[1] for r in rows.values())
-    for k, (n, t, a, m) in sorted(rows.items(), key=lambda kv: -kv[1][1]):
+    for k, (n, t, a, m, mx) in sorted(rows.items(), key=lambda kv: -kv[1][1]):
         if filt and filt not in k:
             continue
         short = k.split("(")[0].replace("void ", "").replace("rph::", "")[:70]
-        print(f"{short:70s} n={n:5d} tot={t / 1e3:9.1f}us mean={a / 1e3:7.2f}us min={m / 1e3:7.2f}us {100 * t / tot:5.1f}%")
+        print(f"{short:70s} n={n:5d} tot={t / 1e3:9.1f}us mean={a / 1e3:7.2f}us min={m / 1e3:7.2f}us "
+              f"max={mx / 1e3:7.2f}us {100 * t / tot:5.1f}%")
 
 
 if __name__ == "__main__":

@@ -28,11 +28,20 @@ def main():
         seg = "explore" if gy > 1 else ("first" if i < first_eval else "later")
         k = name.split("(")[0].replace("_ZN3rph", "").split("E")[0][:24]
         k = "15k_lm_solve_eval" if "k_lm_solve_eval" in name else k
+        # (an exploration solve with a slice of the path scan riding in its launch)
+        k = "14k_lm_solve_sim" if "k_lm_solve_sim" in name else k
         agg[(seg, k)] += (t1 - t0) / 1e3
         cnt[(seg, k)] += 1
     print(f"replay {(rep[-1][2] - rep[0][1]) / 1e3:.1f} us, {len(rep)} kernels, first date "
           f"{(rep[first_eval][1] - rep[0][1]) / 1e3:.1f} us, idle "
           f"{sum(max(0, rep[i + 1][1] - rep[i][2]) for i in range(len(rep) - 1)) / 1e3:.1f} us")
+    # where the fits start: the head of the path scan (k_sim_scan_pair) and whatever else precedes the first
+    # exploration pass, and the polish fit's first pass (grid y = 1), from the start of the replay
+    p0 = next((r for r in rep if "k_lm_pass" in r[0]), None)
+    p1 = next((r for r in rep if "k_lm_pass" in r[0] and r[3] == 1), None)
+    print(f"head launch {(rep[0][2] - rep[0][1]) / 1e3:.1f} us, first k_lm_pass at "
+          f"{(p0[1] - rep[0][1]) / 1e3 if p0 else float('nan'):.1f} us, first one-instance k_lm_pass at "
+          f"{(p1[1] - rep[0][1]) / 1e3 if p1 else float('nan'):.1f} us")
     for k in sorted(agg):
         print(f"  {k[0]:8s} {k[1]:26s} n={cnt[k]:3d} total {agg[k]:8.1f} us  mean {agg[k] / cnt[k]:6.2f} us")
 

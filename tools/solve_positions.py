@@ -24,6 +24,7 @@ def main():
     pos = collections.defaultdict(list)
     cnt = collections.Counter()
     for i, (name, t0, t1) in enumerate(rep[fe:], fe):
+        # ("k_lm_solve" also names k_lm_solve_eval and the first date's k_lm_solve_sim)
         k = next((x for x in ("k_lm_solve", "k_lm_pass", "k_lm_reduce", "k_hedge_eval") if x in name), None)
         if k is None:
             continue

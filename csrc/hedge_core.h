@@ -472,6 +472,43 @@ int with_shape(L list, int nin, int h, int nout, int head, const char* who, F&& 
   return match_shape(list, nin, h, nout, head, &rc, fn) ? rc : rph_report_shape(who, nin, h, nout, head);
 }
 
+// Host-side check of a PnlDesc (run before every launch: a bad descriptor
+// must not reach the GPU).
+inline int validate_pnl(const PnlDesc* d, const char* who) {
+  const int nhold = d->head == HEAD_COMPLEMENT ? 2 : d->nout;
+  if (!d->snap || !d->stats || !d->payoff || !d->fmu || !d->fisd || !d->bond || d->n_local < 1 || d->n_dates < 1 ||
+      d->nin < 1 || d->nin > MAXIN || nhold < 2 || nhold > MAXHOLD)
+    return rph_report(who, "bad P&L descriptor");
+  if (!(d->alpha >= 0.f && d->alpha <= 1.f)) return rph_report(who, "LeakyReLU slope must be in [0, 1]");
+  for (int f = 0; f < d->nin; ++f)
+    if (!d->feat[f] || d->feat_ts[f] < 0) return rph_report(who, "null feature pointer / negative stride");
+  for (int k = 0; k < nhold - 1; ++k)
+    if (!d->price[k] || d->price_ts[k] < d->n_local) return rph_report(who, "null price pointer / bad stride");
+  const long long per_wg = 256LL * PNL_PPT;
+  if ((long long)d->num_wgs * per_wg < d->n_local || (long long)(d->num_wgs - 1) * per_wg >= d->n_local)
+    return rph_report(who, "num_wgs does not match n_local / (256 * PNL_PPT)");
+  if (d->ex_kind != EX_NONE) {  // stopping rule: one network, exercise dates t % ex_every == 0
+    if (d->ex_kind != EX_PUT && d->ex_kind != EX_CALL) return rph_report(who, "ex_kind must be 0, 1 (put) or 2 (call)");
+    if (d->has_b) return rph_report(who, "has_b with ex_kind (early exercise takes one network)");
+    if (d->ex_every < 1) return rph_report(who, "ex_every must be >= 1 with ex_kind");
+    if (!(d->ex_strike == d->ex_strike) || d->ex_strike < 0.f || d->ex_strike > 3.0e38f)
+      return rph_report(who, "ex_strike must be finite and >= 0");
+  } else if (d->tau_out) {
+    return rph_report(who, "tau_out without ex_kind");
+  }
+  return 0;
+}
+
+// Host-side check of the CostTerms beside a forward scan's descriptor
+// (rph_pnl_cost, rph_oos_cost).
+inline int validate_cost(const CostTerms* c, const char* who) {
+  if (!(c->cost_rate >= 0.f && c->cost_rate <= 3.0e38f)) return rph_report(who, "cost_rate must be finite and >= 0");
+  if (c->cost_rate > 1.f) return rph_report(who, "cost_rate must be <= 1");
+  if (!(c->band >= 0.f && c->band <= 3.0e38f)) return rph_report(who, "band must be finite and >= 0");
+  if (!c->cstats) return rph_report(who, "null cstats");
+  return 0;
+}
+
 // Host-side check of a training descriptor against what the kernels and their
 // grids assume (run before every launch: a bad shape must not reach the GPU).
 // mode: 0 ticket step, 1 lagged step / finalize, 2 persistent fit.

@@ -28,6 +28,7 @@
 #include "hedge_fit.h"
 #include "hedge_lag.h"
 #include "hedge_narrow.h"
+#include "pnl_scan.h"
 
 #include <type_traits>
 
@@ -214,219 +215,14 @@ __global__ __launch_bounds__(256) void k_hedge_eval(const EvalDesc d) {
 }
 
 // ---------------------------------------------------------------------------
-// Self-financing hedge P&L scan (PnlDesc, rph_types.h): one thread per path
-// (PNL_PPT paths per thread), dates in lockstep per workgroup so each date's
-// network(s) are staged once in LDS; the path inputs run one date ahead.  Wealth starts at V_0, holds the traded-
-// asset holdings of date t's network and keeps the remainder in the bank
-// account; P&L_T = W_T - liability.  Per-workgroup fp64 statistics in the
-// eval-stats layout (ES_V = W_T, ES_RES = P&L).  Not a hot path (one pass per
-// run, a few hundred VALU flops per path and date); the corrected counterpart
-// of the reference's one-step "P&L" (Q24, Replicating_Portfolio.py:120).
+// Self-financing hedge P&L scan (PnlDesc, rph_types.h): the body is pnl_scan
+// (pnl_scan.h), shared with the scan under transaction costs (hedge_cost.hip).
+// EX: the stopping rule of an early-exercise run (PnlDesc.ex_kind).
 // ---------------------------------------------------------------------------
-
-// EX: the stopping rule of an early-exercise run (PnlDesc.ex_kind): a path is
-// frozen at its first exercise date; the workgroup still walks every date in
-// lockstep (the weights of a date are staged once for all its paths).
 template <int NIN, int H, int NO, int HEAD, bool EX = false>
 __global__ __launch_bounds__(256) void k_hedge_pnl(const PnlDesc d) {
-  using S = NetShape<NIN, H, NO, HEAD>;
-  constexpr int NHOLD = S::NHOLD;
-  constexpr int NA = NHOLD - 1;  // traded assets (the last holding is the bank account)
-  constexpr int WBOFF = (S::P + 3) / 4 * 4;
   prefetch_kernarg<sizeof(PnlDesc)>();
-  RPH_DASSERT(d.n_local > 0 && d.num_wgs == (int)gridDim.x && d.snap != nullptr && d.stats != nullptr);
-  __shared__ __attribute__((aligned(16))) float wl[WBOFF + S::P + 4];
-  __shared__ double sred[4][EX ? 12 : 8];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const long long base = (long long)blockIdx.x * 256 * PNL_PPT + tid;
-  const bool has_b = d.has_b != 0;
-  // per path: wealth, the traded prices at the current date (carried to the
-  // next date: each price row is loaded once) and the next date's inputs,
-  // all loads of a date issued together before any compute
-  float wealth[PNL_PPT], s_cur[PNL_PPT][NA > 0 ? NA : 1];
-  long long pidx[PNL_PPT];
-#pragma unroll
-  for (int j = 0; j < PNL_PPT; ++j) {
-    const long long p = base + (long long)j * 256;
-    const bool ok = p < d.n_local;
-    pidx[j] = ok ? p : 0;  // invalid paths compute on path 0 and are never stored
-    wealth[j] = ok ? (d.w0 ? d.w0[p] : d.wealth0) : 0.f;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) s_cur[j][a] = d.price[a][pidx[j]];
-  }
-  // date t's inputs are loaded one date ahead (software pipeline): their
-  // latency hides under date t-1's network evaluation
-  float xr[PNL_PPT][NIN], s_nxt[PNL_PPT][NA > 0 ? NA : 1];
-  auto load_date = [&](int t) {
-#pragma unroll
-    for (int j = 0; j < PNL_PPT; ++j) {
-#pragma unroll
-      for (int f = 0; f < NIN; ++f) xr[j][f] = d.feat[f][(long long)t * d.feat_ts[f] + pidx[j]];
-#pragma unroll
-      for (int a = 0; a < NA; ++a) s_nxt[j][a] = d.price[a][(long long)(t + 1) * d.price_ts[a] + pidx[j]];
-    }
-  };
-  // early exercise: a path's exercise date (n_dates: alive), its P&L and the
-  // amount it was paid, discounted to date 0
-  [[maybe_unused]] int tau[PNL_PPT];
-  [[maybe_unused]] float pnl_ex[PNL_PPT];
-  [[maybe_unused]] double paid[PNL_PPT];
-  if constexpr (EX) {
-#pragma unroll
-    for (int j = 0; j < PNL_PPT; ++j) {
-      tau[j] = d.n_dates;
-      pnl_ex[j] = 0.f;
-      paid[j] = 0.0;
-    }
-  }
-  if (d.n_dates > 0) load_date(0);
-  for (int t = 0; t < d.n_dates; ++t) {
-    float xc[PNL_PPT][NIN], sc_nxt[PNL_PPT][NA > 0 ? NA : 1];
-#pragma unroll
-    for (int j = 0; j < PNL_PPT; ++j) {
-#pragma unroll
-      for (int f = 0; f < NIN; ++f) xc[j][f] = xr[j][f];
-#pragma unroll
-      for (int a = 0; a < NA; ++a) sc_nxt[j][a] = s_nxt[j][a];
-    }
-    if (t + 1 < d.n_dates) load_date(t + 1);
-    __syncthreads();  // every thread is done with date t-1's weights
-    const NetWeights* wt = d.snap + (size_t)t * 2;
-    for (int i = tid; i < S::P; i += 256) {
-      wl[i] = wt[0].w[0][i];
-      if (has_b) wl[WBOFF + i] = wt[1].w[0][i];
-    }
-    float mu[NIN], isd[NIN];
-#pragma unroll
-    for (int f = 0; f < NIN; ++f) {
-      mu[f] = d.fmu[t * MAXIN + f];
-      isd[f] = d.fisd[t * MAXIN + f];
-    }
-    const float grow = (float)(d.bond[t + 1] / d.bond[t]);
-    [[maybe_unused]] bool ex_date = false;
-    [[maybe_unused]] float bond_t = 0.f, to_end = 0.f;
-    [[maybe_unused]] double disc = 0.0;
-    if constexpr (EX) {
-      ex_date = t % d.ex_every == 0;
-      bond_t = (float)d.bond[t];
-      to_end = (float)(d.bond[d.n_dates] / d.bond[t]);
-      disc = d.bond[0] / d.bond[t];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PNL_PPT; ++j) {
-      uint32_t zo = 0;  // opaque zero: weights stay in LDS (broadcast reads), not hoisted into VGPRs
-      asm volatile("" : "+v"(zo));
-      const float* __restrict__ WA = (const float*)__builtin_assume_aligned(wl + (zo & ~3u), 16);
-      const float* __restrict__ WB = (const float*)__builtin_assume_aligned(wl + WBOFF + (zo & ~3u), 16);
-      float x[NIN];
-#pragma unroll
-      for (int f = 0; f < NIN; ++f) x[f] = (xc[j][f] - mu[f]) * isd[f];
-      float z1[H], a1[H], z2[H], a2[H], hold[NHOLD], hb[NHOLD];
-      net_forward<NIN, H, NO, HEAD>(WA, x, d.alpha, z1, a1, z2, a2, hold);
-      if (has_b) {
-        net_forward<NIN, H, NO, HEAD>(WB, x, d.alpha, z1, a1, z2, a2, hb);
-#pragma unroll
-        for (int k = 0; k < NHOLD; ++k) hold[k] = hold[k] + d.hold_c * (hb[k] - hold[k]);
-      }
-      if constexpr (EX) {
-        if (ex_date && tau[j] == d.n_dates) {
-          // continuation value of date t's network in the eval kernel's operation order
-          float c = 0.f;
-#pragma unroll
-          for (int a = 0; a < NA; ++a) c = fmaf(hold[a], s_cur[j][a], c);
-          c = fmaf(hold[NHOLD - 1], bond_t, c);
-          const float s0 = s_cur[j][0];
-          const float xv = d.ex_kind == EX_PUT ? fmaxf(d.ex_strike - s0, 0.f) : fmaxf(s0 - d.ex_strike, 0.f);
-          if (xv > 0.f && xv >= c) {
-            tau[j] = t;
-            pnl_ex[j] = (wealth[j] - xv) * to_end;
-            paid[j] = (double)xv * disc;
-            wealth[j] = wealth[j] * to_end;  // W_tau carried in the bank account to the horizon
-          }
-        }
-      }
-      float w = wealth[j] * grow;
-#pragma unroll
-      for (int a = 0; a < NA; ++a) {
-        w = fmaf(hold[a], sc_nxt[j][a] - s_cur[j][a] * grow, w);
-        s_cur[j][a] = sc_nxt[j][a];
-      }
-      if constexpr (EX) wealth[j] = tau[j] == d.n_dates ? w : wealth[j];  // an exercised path is frozen
-      else wealth[j] = w;
-    }
-  }
-  // P&L and per-workgroup fp64 statistics
-  double sv = 0, sv2 = 0, sp = 0, sp2 = 0, sa = 0, cnt = 0;
-  float pmin = INFINITY, pmax = -INFINITY;
-  [[maybe_unused]] double sx = 0, sxv = 0, stau = 0;
-#pragma unroll
-  for (int j = 0; j < PNL_PPT; ++j) {
-    const long long p = base + (long long)j * 256;
-    if (p >= d.n_local) continue;
-    float pnl = wealth[j] - d.payoff[p];
-    if constexpr (EX) {
-      const bool exd = tau[j] < d.n_dates;
-      if (exd) pnl = pnl_ex[j];
-      if (d.tau_out) d.tau_out[p] = tau[j];
-      sx += exd ? 1.0 : 0.0;
-      sxv += exd ? paid[j] : (double)d.payoff[p] * (d.bond[0] / d.bond[d.n_dates]);
-      stau += (double)tau[j];
-    }
-    if (d.pnl_out) d.pnl_out[p] = pnl;
-    sv += wealth[j];
-    sv2 += (double)wealth[j] * wealth[j];
-    sp += pnl;
-    sp2 += (double)pnl * pnl;
-    sa += fabsf(pnl);
-    cnt += 1.0;
-    pmin = fminf(pmin, pnl);
-    pmax = fmaxf(pmax, pnl);
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    sv += __shfl_xor(sv, o, 64);
-    sv2 += __shfl_xor(sv2, o, 64);
-    sp += __shfl_xor(sp, o, 64);
-    sp2 += __shfl_xor(sp2, o, 64);
-    sa += __shfl_xor(sa, o, 64);
-    cnt += __shfl_xor(cnt, o, 64);
-    pmin = fminf(pmin, __shfl_xor(pmin, o, 64));
-    pmax = fmaxf(pmax, __shfl_xor(pmax, o, 64));
-    if constexpr (EX) {
-      sx += __shfl_xor(sx, o, 64);
-      sxv += __shfl_xor(sxv, o, 64);
-      stau += __shfl_xor(stau, o, 64);
-    }
-  }
-  if constexpr (EX) {
-    if (lane == 0) {
-      sred[wid][8] = sx; sred[wid][9] = sxv; sred[wid][10] = stau;
-    }
-  }
-  if (lane == 0) {
-    sred[wid][0] = sv; sred[wid][1] = sv2; sred[wid][2] = sp; sred[wid][3] = sp2;
-    sred[wid][4] = sa; sred[wid][5] = cnt; sred[wid][6] = pmin; sred[wid][7] = pmax;
-  }
-  __syncthreads();
-  if (tid < EVAL_NSTAT) {
-    double v = 0.0;
-    auto sum4 = [&](int k) { return (sred[0][k] + sred[1][k]) + (sred[2][k] + sred[3][k]); };
-    if (tid == ES_V) v = sum4(0);
-    else if (tid == ES_V2) v = sum4(1);
-    else if (tid == ES_RES) v = sum4(2);
-    else if (tid == ES_RES2) v = sum4(3);
-    else if (tid == ES_ABSRES) v = sum4(4);
-    else if (tid == ES_COUNT) v = sum4(5);
-    else if (tid == ES_RESMIN) v = fmin(fmin(sred[0][6], sred[1][6]), fmin(sred[2][6], sred[3][6]));
-    else if (tid == ES_RESMAX) v = fmax(fmax(sred[0][7], sred[1][7]), fmax(sred[2][7], sred[3][7]));
-    if constexpr (EX) {
-      if (tid == ES_EXER) v = sum4(8);
-      else if (tid == ES_EXVAL) v = sum4(9);
-      else if (tid == ES_TAU) v = sum4(10);
-    }
-    d.stats[(size_t)blockIdx.x * EVAL_NSTAT + tid] = v;
-  }
+  pnl_scan<NIN, H, NO, HEAD, EX, false>(d, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -651,28 +447,8 @@ extern "C" int rph_eval(const EvalDesc* d, void* stream) {
 }
 
 extern "C" int rph_pnl(const PnlDesc* d, void* stream) {
-  const int nhold = d->head == HEAD_COMPLEMENT ? 2 : d->nout;
-  if (!d->snap || !d->stats || !d->payoff || !d->fmu || !d->fisd || !d->bond || d->n_local < 1 || d->n_dates < 1 ||
-      d->nin < 1 || d->nin > MAXIN || nhold < 2 || nhold > MAXHOLD)
-    return rph_report("rph_pnl", "bad P&L descriptor");
-  if (!(d->alpha >= 0.f && d->alpha <= 1.f)) return rph_report("rph_pnl", "LeakyReLU slope must be in [0, 1]");
-  for (int f = 0; f < d->nin; ++f)
-    if (!d->feat[f] || d->feat_ts[f] < 0) return rph_report("rph_pnl", "null feature pointer / negative stride");
-  for (int k = 0; k < nhold - 1; ++k)
-    if (!d->price[k] || d->price_ts[k] < d->n_local) return rph_report("rph_pnl", "null price pointer / bad stride");
-  const long long per_wg = 256LL * PNL_PPT;
-  if ((long long)d->num_wgs * per_wg < d->n_local || (long long)(d->num_wgs - 1) * per_wg >= d->n_local)
-    return rph_report("rph_pnl", "num_wgs does not match n_local / (256 * PNL_PPT)");
+  if (int rc = validate_pnl(d, "rph_pnl")) return rc;
   const bool ex = d->ex_kind != EX_NONE;
-  if (ex) {  // stopping rule: one network, exercise dates t % ex_every == 0
-    if (d->ex_kind != EX_PUT && d->ex_kind != EX_CALL) return rph_report("rph_pnl", "ex_kind must be 0, 1 (put) or 2 (call)");
-    if (d->has_b) return rph_report("rph_pnl", "has_b with ex_kind (early exercise takes one network)");
-    if (d->ex_every < 1) return rph_report("rph_pnl", "ex_every must be >= 1 with ex_kind");
-    if (!(d->ex_strike == d->ex_strike) || d->ex_strike < 0.f || d->ex_strike > 3.0e38f)
-      return rph_report("rph_pnl", "ex_strike must be finite and >= 0");
-  } else if (d->tau_out) {
-    return rph_report("rph_pnl", "tau_out without ex_kind");
-  }
   hipStream_t s = (hipStream_t)stream;
   return with_shape(AllShapes{}, d->nin, d->h, d->nout, d->head, "rph_pnl", [&](auto t) {
     using T = decltype(t);

@@ -62,6 +62,11 @@ namespace rph {
 #define RPH_FIELDS_SimRideDesc(X, T) \
   X(T, sim) X(T, pay_out) X(T, pay_out2) X(T, strike) X(T, pay_kind) X(T, b0) X(T, b1) X(T, per_rider) X(T, pad_ride)
 
+#define RPH_FIELDS_CostTerms(X, T) \
+  X(T, cost_rate) X(T, band) X(T, unwind) X(T, pad) X(T, cost_out) X(T, turn_out) X(T, trades_out) X(T, cstats)
+#define RPH_FIELDS_CostPnlDesc(X, T) X(T, p) X(T, c)
+#define RPH_FIELDS_CostOosDesc(X, T) X(T, o) X(T, c)
+
 #define RPH_DESCRIPTORS(X) \
   X(TrainDesc) X(EvalDesc) X(PnlFinishDesc) X(PnlDesc) X(LmDpDesc) X(LmDesc) X(SimDesc)
 // Descriptors of later kernels, in a table of their own (rph_layout_fields_ext;
@@ -71,6 +76,8 @@ namespace rph {
 #define RPH_DESCRIPTORS_RIDE(X) X(SelfTargetDesc)
 // ... and of the sim ride (rph_layout_fields_sim; native.py DESCRIPTORS_SIM)
 #define RPH_DESCRIPTORS_SIM(X) X(SimRideDesc)
+// ... and of the scans under transaction costs (rph_layout_fields_cost; native.py DESCRIPTORS_COST)
+#define RPH_DESCRIPTORS_COST(X) X(CostTerms) X(CostPnlDesc) X(CostOosDesc)
 
 struct FieldRow {
   const char* strct;
@@ -84,6 +91,7 @@ constexpr FieldRow kFieldRows[] = {RPH_DESCRIPTORS(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsExt[] = {RPH_DESCRIPTORS_EXT(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsRide[] = {RPH_DESCRIPTORS_RIDE(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsSim[] = {RPH_DESCRIPTORS_SIM(RPH_STRUCT_ROWS)};
+constexpr FieldRow kFieldRowsCost[] = {RPH_DESCRIPTORS_COST(RPH_STRUCT_ROWS)};
 
 // The listed fields of `strct` start at 0, follow each other with no gap and
 // end at `size`: with no implicit padding in the struct, none is left out.
@@ -109,10 +117,12 @@ constexpr bool layout_covers(const FieldRow (&rows)[N], const char* strct, size_
 #define RPH_STRUCT_COVERED_EXT(T) RPH_STRUCT_COVERED_IN(kFieldRowsExt, T)
 #define RPH_STRUCT_COVERED_RIDE(T) RPH_STRUCT_COVERED_IN(kFieldRowsRide, T)
 #define RPH_STRUCT_COVERED_SIM(T) RPH_STRUCT_COVERED_IN(kFieldRowsSim, T)
+#define RPH_STRUCT_COVERED_COST(T) RPH_STRUCT_COVERED_IN(kFieldRowsCost, T)
 RPH_DESCRIPTORS(RPH_STRUCT_COVERED)
 RPH_DESCRIPTORS_EXT(RPH_STRUCT_COVERED_EXT)
 RPH_DESCRIPTORS_RIDE(RPH_STRUCT_COVERED_RIDE)
 RPH_DESCRIPTORS_SIM(RPH_STRUCT_COVERED_SIM)
+RPH_DESCRIPTORS_COST(RPH_STRUCT_COVERED_COST)
 
 // Constants, by their names in rphedge/ops/layout.py.
 struct ConstRow {
@@ -160,6 +170,13 @@ constexpr ConstRow kConstRows[] = {
     RPH_FLOAT_INDEX(F_APE_SUM, FitState, ape_sum) RPH_FLOAT_INDEX(F_LAST_LOSS, FitState, last_loss)
     RPH_FLOAT_INDEX(F_LAST_MAE, FitState, last_mae) RPH_FLOAT_INDEX(F_LAST_MAPE, FitState, last_mape)
     RPH_FLOAT_INDEX(F_RESTORE_END, FitState, restore_at_end) RPH_FLOAT_INDEX(F_HIST, FitState, hist)
+};
+
+// ... and the constants of the cost scans, by their names in rphedge/ops/layout_cost.py
+// (a table of its own: rph_layout_consts_cost).
+constexpr ConstRow kConstRowsCost[] = {
+    RPH_CONST(COST_NSTAT) RPH_CONST(CS_COST) RPH_CONST(CS_COST2) RPH_CONST(CS_TURN) RPH_CONST(CS_TRADES)
+    RPH_CONST(CS_COUNT)
 };
 
 }  // namespace rph

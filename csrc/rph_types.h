@@ -544,6 +544,41 @@ struct OosDesc {
   int nin, h, nout, head;
 };
 
+// Proportional transaction costs and a no-trade band on the forward scans
+// (k_hedge_pnl_cost, k_hedge_oos_cost; hedge_cost.hip).  Per path and traded
+// asset a the held position starts at h_a,-1 = 0 and follows the network's
+// target phi*_a,t only where it leaves the band:
+//   h_a,t = phi*_a,t  if t == 0 or |phi*_a,t - h_a,t-1| > band,  else h_a,t-1
+// (fp32 comparison; band = 0 always trades).  Date t costs
+//   c_t = cost_rate sum_a |h_a,t - h_a,t-1| S_a,t     (ascending a, fmaf)
+// which leaves the wealth before the scan's update, W <- W - c_t; with
+// `unwind` the final position is sold at the horizon, c_n = cost_rate sum_a
+// |h_a,n-1| S_a,n off W_T.  cost_rate = band = unwind = 0 is bitwise the plain scan.
+constexpr int COST_NSTAT = 8;  // doubles per workgroup in the cost stats slab
+enum CostStat : int {
+  CS_COST = 0,    // sum of cost_T = sum_t c_t (float)(B_n / B_t), the cost carried to the horizon
+  CS_COST2 = 1,   // sum of cost_T^2
+  CS_TURN = 2,    // sum of the turnover sum_t sum_a |dh| S_a,t (the unwinding sale included)
+  CS_TRADES = 3,  // sum of the dates t >= 1 on which a path traded at least one asset
+  CS_COUNT = 4    // paths; rows 5..7 are zero
+};
+struct CostTerms {
+  float cost_rate, band;
+  int unwind, pad;
+  float* cost_out;               // per-path cost_T [n_local] (may be null)
+  float* turn_out;               // per-path turnover [n_local] (may be null)
+  int* trades_out;               // per-path trade dates [n_local] (may be null)
+  double* cstats;                // [num_wgs][COST_NSTAT]
+};
+struct CostPnlDesc {
+  PnlDesc p;                     // the scan (ex_kind = EX_NONE: no early exercise with costs)
+  CostTerms c;
+};
+struct CostOosDesc {
+  OosDesc o;
+  CostTerms c;
+};
+
 // The run's scan split over the launches of a first date's multi-start
 // exploration (the sim ride).  The exploration reads only the first paths of
 // the shard, so a head launch simulates the 256-path blocks [0, b0) (with the

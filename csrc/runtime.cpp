@@ -68,6 +68,16 @@ extern "C" int rph_layout_fields_sim(const FieldRow** rows) {
   return (int)(sizeof(kFieldRowsSim) / sizeof(kFieldRowsSim[0]));
 }
 
+extern "C" int rph_layout_fields_cost(const FieldRow** rows) {
+  *rows = kFieldRowsCost;
+  return (int)(sizeof(kFieldRowsCost) / sizeof(kFieldRowsCost[0]));
+}
+
+extern "C" int rph_layout_consts_cost(const ConstRow** rows) {
+  *rows = kConstRowsCost;
+  return (int)(sizeof(kConstRowsCost) / sizeof(kConstRowsCost[0]));
+}
+
 extern "C" int rph_layout_consts(const ConstRow** rows) {
   *rows = kConstRows;
   return (int)(sizeof(kConstRows) / sizeof(kConstRows[0]));

@@ -5,6 +5,8 @@
              [--exercise bermudan [--exercise-every K]]   ... with the right to exercise at every K-th rebalancing date
   run / european also take the out-of-sample test of the trained hedge:
              [--oos-paths-log2 M] [--oos-seed S] [--oos-stress key=value ...]   2^M fresh paths (stress: sigma=0.18 ...)
+  run / european also take proportional transaction costs and a no-trade band (RunResult.costs):
+             [--cost-rate R] [--rebalance-band B] [--cost-unwind]   a trade of |dh| at S costs R |dh| S
   sts                                                    Single Time Step notebook driver
   sweep      [--sigmas .05,.1,...]                       volatility sweep (Multi Time Step)
   calibrate  --csv prices.csv | --synthetic               CIR calibration (Extra: Stochastic Volatility)
@@ -35,6 +37,8 @@ def _summary(res) -> dict:
     out = {"phi0": res.phi, "psi0": res.psi, "V0": res.v0, "terminal_pnl": res.terminal_pnl, "VaR": res.var,
            "summary": {k: v for k, v in res.summary.items() if not isinstance(v, list)},
            "timings": res.timings}
+    if res.costs is not None:
+        out["costs"] = res.costs
     if res.out_of_sample is not None:
         out["out_of_sample"] = res.out_of_sample.as_dict()
     return out
@@ -46,6 +50,25 @@ def _oos_args(p):
     p.add_argument("--oos-seed", type=int, default=None, help="Sobol scramble seed of the test paths")
     p.add_argument("--oos-stress", nargs="*", default=None, metavar="key=value",
                    help="simulate the test paths under other model parameters (sigma=0.18, xi=0.4 ...)")
+
+
+def _cost_args(p):
+    p.add_argument("--cost-rate", type=float, default=None,
+                   help="proportional transaction cost per unit of traded value (the hedge is scanned under it)")
+    p.add_argument("--rebalance-band", type=float, default=None,
+                   help="no-trade band: rebalance only where the target leaves the held position by more than this")
+    p.add_argument("--cost-unwind", action="store_true", help="also sell the final position at the horizon")
+
+
+def _cost_params(a) -> dict:
+    out = {}
+    if a.cost_rate is not None:
+        out["cost_rate"] = a.cost_rate
+    if a.rebalance_band is not None:
+        out["rebalance_band"] = a.rebalance_band
+    if a.cost_unwind:
+        out["cost_unwind"] = True
+    return out
 
 
 def _oos_params(a) -> dict:
@@ -78,6 +101,7 @@ def main(argv=None) -> int:
     r.add_argument("--out", default=None)
     r.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
     _oos_args(r)
+    _cost_args(r)
     e = sub.add_parser("european")
     e.add_argument("--paths", type=int, default=3000)
     e.add_argument("--rebalancing", type=float, default=1 / 52)
@@ -90,6 +114,7 @@ def main(argv=None) -> int:
     e.add_argument("--set", nargs="*", default=[])
     e.add_argument("--plots", default=None, help="directory for the report figures (C26-C32)")
     _oos_args(e)
+    _cost_args(e)
     sub.add_parser("sts").add_argument("--no-parity", action="store_true")
     s = sub.add_parser("sweep")
     s.add_argument("--sigmas", default="0.05,0.10,0.15,0.20,0.30")
@@ -112,6 +137,7 @@ def main(argv=None) -> int:
         if a.out:
             params["save_dir"] = a.out
         params.update(_oos_params(a))
+        params.update(_cost_params(a))
         res = run_params(params, sv=a.sv)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))
@@ -126,6 +152,7 @@ def main(argv=None) -> int:
         if a.exercise_every is not None:
             extra["exercise_every"] = a.exercise_every
         extra.update(_oos_params(a))
+        extra.update(_cost_params(a))
         res = european_option(N_paths=a.paths, rebalancing_frequency=a.rebalancing, parity=a.parity, **extra)
         _plots(res, a.plots)
         print(json.dumps(_summary(res), default=float, indent=1))

@@ -108,7 +108,8 @@ def _moments(x, world: int = 1):
 
 
 def bs_delta_hedge(S, bond, strike: float, r: float, sigma: float, T: float, times,
-                   option_type: str = "CALL", payoff=None, world: int = 1) -> dict:
+                   option_type: str = "CALL", payoff=None, world: int = 1, cost_rate: float = 0.0, band: float = 0.0,
+                   unwind: bool = False, sigma_hedge: float | None = None) -> dict:
     """Black–Scholes delta hedge of a European option on the SAME simulated
     coarse grid — the analytic anchor for the learnt hedge's P&L.
 
@@ -118,7 +119,17 @@ def bs_delta_hedge(S, bond, strike: float, r: float, sigma: float, T: float, tim
     bank account (self-financing), P&L_T = W_T - payoff(S_T).  Also returns the
     one-step residual of the last date (the reference's "P&L", Q24) of the
     BS replicating portfolio (Δ S + (V - Δ S)/B B).  Values are normalised
-    (multiply by S0).  float64 throughout; moments pooled over ranks."""
+    (multiply by S0).  float64 throughout; moments pooled over ranks.
+
+    ``cost_rate`` / ``band`` / ``unwind``: the same hedge under proportional
+    transaction costs and a no-trade band (the semantics of ``engine.Costs``:
+    the held delta follows Δ_BS where ``t == 0``, ``band == 0`` or it differs
+    by more than ``band``; a trade costs ``cost_rate |dh| S_t``, taken off the
+    wealth before the update); the result then also carries ``mean_cost``
+    (carried to the horizon), ``mean_turnover`` and ``trades_per_path``.
+    ``sigma_hedge``: the volatility of the hedge ratio (:func:`leland_sigma`;
+    the initial wealth stays the BS price at ``sigma``).  The defaults are
+    the frictionless hedge, unchanged."""
     import torch
 
     S = S.double()
@@ -130,7 +141,7 @@ def bs_delta_hedge(S, bond, strike: float, r: float, sigma: float, T: float, tim
         payoff = (strike - S[-1]).clamp_min(0) if put else (S[-1] - strike).clamp_min(0)
     payoff = payoff.double()
 
-    def price_delta(s, tau):
+    def price_delta(s, tau, sigma=sigma):
         if tau <= 0:
             itm = (s < strike) if put else (s > strike)
             return ((strike - s).clamp_min(0) if put else (s - strike).clamp_min(0)), \
@@ -145,18 +156,54 @@ def bs_delta_hedge(S, bond, strike: float, r: float, sigma: float, T: float, tim
             return strike * disc * (1 - Nd2) - s * (1 - Nd1), Nd1 - 1.0
         return s * Nd1 - strike * disc * Nd2, Nd1
 
+    for name, v in (("cost_rate", cost_rate), ("band", band)):
+        if not math.isfinite(v) or v < 0:
+            raise ValueError(f"bs_delta_hedge: {name} must be finite and >= 0, got {v!r}")
+    frictions = cost_rate > 0 or band > 0 or unwind or sigma_hedge is not None
+    sh = sigma if sigma_hedge is None else float(sigma_hedge)
     v0, _ = price_delta(S[0], T - tt[0])
     w = v0.clone()
+    held = torch.zeros_like(S[0])
+    cost_T, turn, trades = torch.zeros_like(held), torch.zeros_like(held), torch.zeros_like(held)
     for t in range(n_c - 1):
-        _, dl = price_delta(S[t], T - tt[t])
         g = float(B[t + 1] / B[t])
-        w = w * g + dl * (S[t + 1] - S[t] * g)
+        if not frictions:
+            _, dl = price_delta(S[t], T - tt[t])
+            w = w * g + dl * (S[t + 1] - S[t] * g)
+            continue
+        _, dl = price_delta(S[t], T - tt[t], sh)
+        tr = torch.ones_like(held, dtype=torch.bool) if (t == 0 or band == 0) else (dl - held).abs() > band
+        new = torch.where(tr, dl, held)
+        dv = (new - held).abs() * S[t]
+        c = cost_rate * dv
+        cost_T, turn = cost_T + c * float(B[-1] / B[t]), turn + dv
+        if t > 0:
+            trades = trades + tr.double()
+        held = new
+        w = (w - c) * g + held * (S[t + 1] - S[t] * g)
+    if frictions and unwind:
+        dv = held.abs() * S[-1]
+        w, cost_T, turn = w - cost_rate * dv, cost_T + cost_rate * dv, turn + dv
     pnl = w - payoff
     vl, dl = price_delta(S[n_c - 2], T - tt[n_c - 2])
     resid = payoff - (dl * S[-1] + (vl - dl * S[n_c - 2]) / B[n_c - 2] * B[-1])
     pm, ps = _moments(pnl, world)
     _, rs = _moments(resid, world)
-    return {"price": float(v0.mean()), "pnl_mean": pm, "pnl_std": ps, "residual_std_last": rs, "n_dates": n_c - 1}
+    out = {"price": float(v0.mean()), "pnl_mean": pm, "pnl_std": ps, "residual_std_last": rs, "n_dates": n_c - 1}
+    if frictions:
+        out["mean_cost"], out["mean_turnover"] = _moments(cost_T, world)[0], _moments(turn, world)[0]
+        out["trades_per_path"] = _moments(trades, world)[0]
+    return out
+
+
+def leland_sigma(sigma: float, cost_rate: float, dt: float) -> float:
+    """Leland's (1985) hedging volatility for a short option position rebalanced
+    every ``dt`` under the proportional cost ``cost_rate`` per unit traded value:
+    ``sigma sqrt(1 + sqrt(8 / pi) cost_rate / (sigma sqrt(dt)))`` (``cost_rate``
+    is the one-way rate of ``engine.Costs``; the round trip costs twice it)."""
+    if not (sigma > 0 and dt > 0 and cost_rate >= 0):
+        raise ValueError(f"leland_sigma: sigma > 0, dt > 0 and cost_rate >= 0, got {sigma!r}, {dt!r}, {cost_rate!r}")
+    return sigma * math.sqrt(1.0 + math.sqrt(8.0 / math.pi) * cost_rate / (sigma * math.sqrt(dt)))
 
 
 # ---------------------------------------------------------------------------

@@ -22,7 +22,7 @@ import torch
 from . import risk
 from .config import RunConfig, parse_params
 from .driver import BackwardInduction, InductionConfig, InductionResult, error_history, expected_value_trajectory
-from .engine import Exercise, TrainConfig, gram_subsample, make_backend, set_weights
+from .engine import Costs, Exercise, TrainConfig, gram_subsample, make_backend, set_weights
 from .models import hedge_mlp as hm
 from .ops import layout as L
 from .ops import paths as P
@@ -55,6 +55,10 @@ class RunResult:
     policy_value: float | None = None       # mean discounted amount paid under that rule: the policy's own price, a
                                             # lower bound of the option value (the paths are risk-neutral)
     tree_price: float | None = None         # binomial tree with the same exercise dates (GBM runs)
+    costs: dict | None = None               # the hedge under transaction costs (cost_rate / rebalance_band; None: off):
+                                            # rate, band, unwind, net_pnl_mean / _std / _min / _max, gross_pnl_std,
+                                            # mean_cost (at the horizon), cost_share_of_v0, mean_turnover,
+                                            # trades_per_path; GBM call / put: bs_* and leland_* delta-hedge anchors
     out_of_sample: object = None            # rphedge.oos.OosResult of the reported hedge on fresh paths
                                             # (oos_paths_log2 > 0; None: not asked for)
 
@@ -99,6 +103,7 @@ class HedgeRun:
         self.sim_ride = None
         self.kind = self._kind()
         self.exercise = self._exercise()
+        self.costs = self._costs()
         self.spec = self._spec()
         self.paths = None
         self.gpaths = None  # LM Gram subsample paths (engine.gram_subsample), simulated on every rank
@@ -160,6 +165,65 @@ class HedgeRun:
         if c.parity.complement_head or c.parity.local_residual_pnl or c.parity.raw_features:
             raise ValueError(f"{what} is not available with parity=True (the reference has no early exercise)")
         return Exercise(kind=c.option_type.lower(), strike=float(c.K) / float(c.Y), every=every)
+
+    def _costs(self) -> Costs | None:
+        """The run's transaction costs (None: off), validated."""
+        c = self.cfg
+        if not isinstance(c.cost_unwind, (bool, np.bool_)):
+            raise ValueError(f"cost_unwind must be a bool, got {c.cost_unwind!r}")
+        try:
+            costs = Costs(rate=c.cost_rate, band=c.rebalance_band, unwind=bool(c.cost_unwind))
+        except ValueError as e:
+            raise ValueError(f"cost_rate / rebalance_band: {e}") from None
+        if not costs.active:
+            if costs.unwind:
+                raise ValueError("cost_unwind=True needs cost_rate > 0")
+            return None
+        if self.exercise is not None:
+            raise ValueError(f"cost_rate / rebalance_band are not available with exercise={c.exercise!r} (early "
+                             f"exercise with transaction costs is not supported)")
+        if c.parity.local_residual_pnl:
+            raise ValueError("cost_rate / rebalance_band are not available with parity=True (the reference's one-step "
+                             "P&L has no trading)")
+        return costs
+
+    def cost_report(self, k: Costs, cost_pnl, cost_stats, gross_std: float | None, v0: float) -> dict:
+        """The ``costs`` dict of a scan under the costs ``k`` from its P&L statistics
+        (a DateResult in the eval layout) and reduced cost slab, scaled."""
+        from .ops import layout_cost as LC
+
+        scale = self.scale
+        n = float(cost_stats[LC.CS_COUNT])
+        mean_cost = float(cost_stats[LC.CS_COST]) / n * scale
+        bond = np.asarray(self.paths.bond, np.float64)
+        return {"rate": float(k.rate), "band": float(k.band), "unwind": bool(k.unwind),
+                "net_pnl_mean": cost_pnl.residual_mean * scale, "net_pnl_std": cost_pnl.residual_std * scale,
+                "net_pnl_min": float(cost_pnl.stats[L.ES_RESMIN]) * scale,
+                "net_pnl_max": float(cost_pnl.stats[L.ES_RESMAX]) * scale,
+                "gross_pnl_std": gross_std, "mean_cost": mean_cost,
+                # (the cost carried to the horizon, discounted back to date 0, over the fitted V0)
+                "cost_share_of_v0": mean_cost * float(bond[0] / bond[-1]) / v0 if v0 else float("nan"),
+                "mean_turnover": float(cost_stats[LC.CS_TURN]) / n * scale,
+                "trades_per_path": float(cost_stats[LC.CS_TRADES]) / n}
+
+    def cost_anchors(self, costs: Costs, S, bond, times, world: int = 1) -> dict:
+        """GBM call / put: the BS and the Leland delta hedges on the grid ``S`` under ``costs``, scaled."""
+        c = self.cfg
+        if not (self.kind == "european" and self.path_stat is None and c.model in ("gbm", "gbm_log")):
+            return {}
+        from .analytic import bs_delta_hedge, leland_sigma
+
+        T = float(c.T)
+        kw = dict(option_type=c.option_type, world=world, cost_rate=float(costs.rate), band=float(costs.band),
+                  unwind=bool(costs.unwind))
+        bs = bs_delta_hedge(S, bond, float(c.K) / float(c.Y), c.r, c.sigma, T, times, **kw)
+        out = {"bs_net_pnl_std": bs["pnl_std"] * self.scale, "bs_mean_cost": bs["mean_cost"] * self.scale}
+        if costs.rate > 0:
+            dtc = float(times[1] - times[0])
+            le = bs_delta_hedge(S, bond, float(c.K) / float(c.Y), c.r, c.sigma, T, times,
+                                sigma_hedge=leland_sigma(c.sigma, float(costs.rate), dtc), **kw)
+            out["leland_net_pnl_std"], out["leland_mean_cost"] = le["pnl_std"] * self.scale, le["mean_cost"] * self.scale
+        return out
 
     def _spec(self) -> hm.NetSpec:
         c = self.cfg
@@ -527,7 +591,7 @@ class HedgeRun:
                                init_align=self.init_align(),
                                init_shared_stream=bool(pf.shared_initializer),
                                mean_refit=bool(tr.mean_refit) and not pf.keras_fit_only,
-                               exercise=self.exercise)
+                               exercise=self.exercise, costs=self.costs)
         backend_q = None
         if (self.backend_kind == "hip" and self.di.world == 1 and icfg.q99 and not icfg.shared_q99_model
                 and not icfg.poll_every and tr.concurrent_q99):
@@ -693,18 +757,48 @@ class HedgeRun:
 
     def out_of_sample(self, paths_log2: int | None = None, seed: int | None = None, offset: int = 0,
                       stress: dict | None = None, fused: bool | None = None, keep_pnl: bool = False,
-                      keep_paths: bool = False):
+                      keep_paths: bool = False, costs=None):
         """The trained hedge on paths it has not seen (:func:`rphedge.oos.out_of_sample`):
         ``2^paths_log2`` fresh paths from Sobol index ``offset`` of the stream
         scrambled with ``seed`` (default :data:`rphedge.oos.OOS_SEED`), optionally
         simulated under ``stress``-ed model parameters, hedged with the per-date
         networks, standardisation, strike and bond grid of this run from the
-        fitted V0.  Valid after ``run()``, ``replay()`` or ``resume()``."""
+        fitted V0.  Valid after ``run()``, ``replay()`` or ``resume()``.
+
+        ``costs``: the transaction costs of a second scan of the same paths
+        (``OosResult.costs``; the result's own figures stay frictionless): None =
+        the run's configured costs, an ``engine.Costs`` or a dict of its fields
+        overrides them, False switches them off."""
         from .oos import out_of_sample
 
         self.flush_sim_ride()
         return out_of_sample(self, paths_log2=paths_log2, seed=seed, offset=offset, stress=stress, fused=fused,
-                             keep_pnl=keep_pnl, keep_paths=keep_paths)
+                             keep_pnl=keep_pnl, keep_paths=keep_paths, costs=costs)
+
+    def cost_frontier(self, bands, rate: float | None = None, paths_log2: int | None = None,
+                      seed: int | None = None) -> list:
+        """The cost / risk frontier of the no-trade band: one out-of-sample scan
+        under costs per band of ``bands`` (fused where available: nothing
+        materialised), at ``rate`` (default: the run's ``cost_rate``).  Rows
+        ``{"band", "mean_cost", "net_pnl_std", "net_pnl_mean", "trades_per_path"}``."""
+        from .oos import out_of_sample
+
+        if rate is None:
+            rate = float(self.cfg.cost_rate)
+        bands = [float(b) for b in bands]
+        if not (math.isfinite(rate) and rate > 0):
+            raise ValueError(f"cost_frontier needs a cost rate > 0 (rate=, or the run's cost_rate), got {rate!r}")
+        for b in bands:
+            if not (math.isfinite(b) and b >= 0):
+                raise ValueError(f"cost_frontier: bands must be finite and >= 0, got {b!r}")
+        unwind = bool(self.cfg.cost_unwind)
+        self.flush_sim_ride()
+        rows = []
+        for b in bands:
+            r = out_of_sample(self, paths_log2=paths_log2, seed=seed, costs=Costs(rate=rate, band=b, unwind=unwind),
+                              cost_only=True)
+            rows.append({k: r.costs[k] for k in ("band", "mean_cost", "net_pnl_std", "net_pnl_mean", "trades_per_path")})
+        return rows
 
     def collect(self) -> RunResult:
         c, w = self.cfg, self.di.world
@@ -786,7 +880,12 @@ class HedgeRun:
                                                             c.option_type)
                 summary["tree_boundary"] = [float(b) for b in bnd]
             summary.update(xk)
-        return RunResult(phi=phi, psi=psi, v0=ind.v0 * scale, scale=scale, holdings0=h0, induction=ind,
+        costs = None
+        if self.costs is not None and ind.cost_pnl is not None:
+            costs = self.cost_report(self.costs, ind.cost_pnl, ind.cost_stats, sf["std"] if sf is not None else None, ind.v0 * scale)
+            costs.update(self.cost_anchors(self.costs, self.paths.S, self.paths.bond, self.grid.times(), world=w))
+            summary["net_pnl_std"], summary["mean_cost"] = costs["net_pnl_std"], costs["mean_cost"]
+        return RunResult(phi=phi, psi=psi, v0=ind.v0 * scale, costs=costs, scale=scale, holdings0=h0, induction=ind,
                          errors=error_history(ind), p_e_values=pe, terminal_pnl=tp, var=var, summary=summary,
                          timings=self.timer.summary(), config=c.to_dict(), paths=self.paths,
                          terminal_residual=resid, self_financing_pnl=sf, **xk)

@@ -196,6 +196,12 @@ class RunConfig:
                                      # rebalancing dates t with t % exercise_every == 0, t < the last) | american
                                      # (= bermudan with exercise_every 1: the American option as the grid refines)
     exercise_every: int = 1          # bermudan: every k-th rebalancing date is an exercise date
+    # proportional transaction costs and a no-trade band (engine.Costs; RunResult.costs): with cost_rate > 0 or
+    # rebalance_band > 0 the finished hedge is scanned once more over the training paths under them
+    cost_rate: float = 0.0           # cost per unit of traded value (a trade of |dh| at S costs cost_rate |dh| S), <= 1
+    rebalance_band: float = 0.0      # the position follows the network where it differs from the held one by more
+                                     # than this (units of the holdings output; 0: every date trades)
+    cost_unwind: bool = False        # also sell the final position at the horizon, at the same rate
     # out-of-sample test of the trained hedge (HedgeRun.out_of_sample; RunResult.out_of_sample)
     oos_paths_log2: int = 0          # log2 of the fresh test paths (0: off)
     oos_seed: int | None = None      # Sobol scramble seed of the test paths (None: rphedge.oos.OOS_SEED)

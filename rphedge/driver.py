@@ -23,8 +23,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from .engine import (MAXIN, DateData, Exercise, FitConfig, PnlData, TrainConfig, fit_seed, fit_summary,
-                     geometric_lr_schedule, keras_lr_schedule, pnl_fold_factors, reduce_stats)
+from .engine import (MAXIN, Costs, DateData, Exercise, FitConfig, PnlData, TrainConfig, fit_seed, fit_summary,
+                     geometric_lr_schedule, keras_lr_schedule, pnl_fold_factors, reduce_cost_stats, reduce_stats)
 from .models.hedge_mlp import NetSpec
 from .ops import layout as L
 from .ops.paths import Paths
@@ -95,6 +95,11 @@ class InductionConfig:
     # t % exercise.every == 0 is max(intrinsic, continuation), and the P&L scan
     # stops a path where its holder exercises (None: European)
     exercise: Exercise | None = None
+    # proportional transaction costs and a no-trade band (engine.Costs): after
+    # the induction has closed its P&L, one forward scan of the training paths
+    # under the costs (None / inactive: off).  The induction's own P&L stays
+    # frictionless.  Not with early exercise
+    costs: Costs | None = None
 
 
 @dataclass
@@ -170,6 +175,9 @@ class InductionResult:
     pnl: DateResult | None = None                  # self-financing P&L: stats in the eval layout (ES_RES = P&L)
     pnl_paths: torch.Tensor | None = None          # [n_local] per-path self-financing P&L (keep_paths)
     tau: torch.Tensor | None = None                # [n_local] int32 exercise date of the P&L scan (n_dates: never)
+    cost_pnl: DateResult | None = None             # P&L under InductionConfig.costs: stats in the eval layout
+    cost_stats: np.ndarray | None = None           # [COST_NSTAT] float64 sums of that scan (layout_cost.CS_*)
+    cost_pnl_paths: torch.Tensor | None = None     # [n_local] per-path P&L under the costs (keep_paths)
 
 
 class BackwardInduction:
@@ -292,6 +300,15 @@ class BackwardInduction:
         if ex is not None and icfg.q99:
             raise ValueError("early exercise takes one network per date: q99=True (wts_b / g_base) is not available")
         self.tau = torch.full((n,), self.n_dates, dtype=torch.int32, device=dev) if ex is not None else None
+        # the scan under transaction costs: a band makes the held position depend on
+        # the path's own trading history, so it runs forward, after the induction's P&L
+        self.costs = icfg.costs if (icfg.costs is not None and icfg.costs.active) else None
+        if self.costs is not None:
+            if ex is not None:
+                raise ValueError("transaction costs with early exercise are not supported")
+            self.cost_pnl_stats = backend.new_pnl_stats()
+            self.cost_stats = backend.new_cost_stats()
+            self.cost_pnl_paths = torch.empty(n, dtype=torch.float32, device=dev) if keep else None
 
     def exercise_at(self, t: int) -> Exercise | None:
         """The exercise right at date t (None: the plain epilogue kernel)."""
@@ -503,6 +520,9 @@ class BackwardInduction:
         elif self.pnl_done:
             be.pnl(self.snap, self.pnl_data, self.pnl_stats, has_b=c.q99, hold_c=self.hold_c,
                    pnl_out=self.pnl_paths, exercise=c.exercise, tau_out=self.tau)
+        if self.costs is not None and self.pnl_done:
+            be.pnl(self.snap, self.pnl_data, self.cost_pnl_stats, has_b=c.q99, hold_c=self.hold_c,
+                   pnl_out=self.cost_pnl_paths, costs=self.costs, cost_stats=self.cost_stats)
 
     def collect(self) -> InductionResult:
         c = self.cfg
@@ -527,6 +547,11 @@ class BackwardInduction:
                                  stats=reduce_stats(self.pnl_stats, self.world))
             res.pnl_paths = self.pnl_paths
             res.tau = self.tau
+            if self.costs is not None:
+                res.cost_pnl = DateResult(index=-1, time=res.pnl.time,
+                                          stats=reduce_stats(self.cost_pnl_stats, self.world))
+                res.cost_stats = reduce_cost_stats(self.cost_stats, self.world)
+                res.cost_pnl_paths = self.cost_pnl_paths
         return res
 
 

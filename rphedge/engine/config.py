@@ -256,5 +256,33 @@ class Exercise:
         return torch.clamp(k - s, min=0) if self.kind == "put" else torch.clamp(s - k, min=0)
 
 
+@dataclass(frozen=True)
+class Costs:
+    """Proportional transaction costs and a no-trade band of the forward scans
+    (backends' ``pnl`` / ``oos``; csrc/rph_types.h CostTerms): a trade of
+    ``|dh|`` units at the price ``S`` costs ``rate |dh| S``; the position
+    follows the network's target only where it differs from the held one by
+    more than ``band`` (units of the holdings output; 0 always trades);
+    ``unwind``: the final position is sold at the horizon, at the same rate."""
+
+    rate: float
+    band: float = 0.0
+    unwind: bool = False
+
+    def __post_init__(self):
+        for name in ("rate", "band"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"cost {name} must be a number, got {v!r}")
+            if not np.isfinite(v) or v < 0:
+                raise ValueError(f"cost {name} must be finite and >= 0, got {v!r}")
+        if self.rate > 1:
+            raise ValueError(f"cost rate must be <= 1, got {self.rate!r}")
+
+    @property
+    def active(self) -> bool:
+        return self.rate > 0 or self.band > 0
+
+
 def fit_seed(seed: int, date: int, net: int) -> int:
     return (int(seed) * 1000003 + int(date) * 7919 + int(net) * 104729) & 0xFFFFFFFF

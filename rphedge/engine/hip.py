@@ -9,7 +9,8 @@ import torch
 
 from ..models.hedge_mlp import NetSpec
 from ..ops import layout as L
-from .config import DateData, Exercise, FitConfig, PnlData, TrainConfig
+from ..ops import layout_cost as LC
+from .config import Costs, DateData, Exercise, FitConfig, PnlData, TrainConfig
 from .lm_geometry import (_lm_bias_index, _lm_out_n, gram_subsample, lm_explore_nsub, lm_gram_geometry, lm_og_wgs,
                           lm_out_nu, lm_pass_schedule, lm_shard_gram_wgs, lm_tpack_len)
 from .state import StateBlocks, _Cache, _check_eval_data, _set_norm, _steps, fit_template
@@ -724,11 +725,18 @@ class HipBackend(StateBlocks):
         return ((self.n_local if n_local is None else int(n_local)) + 256 * PNL_PPT - 1) // (256 * PNL_PPT)
 
     def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
-            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None):
+            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None,
+            costs: Costs | None = None, cost_stats=None, cost_out=None, turn_out=None, trades_out=None):
         """Enqueue the self-financing P&L scan (one k_hedge_pnl launch);
         ``exercise``: with the stopping rule, ``tau_out`` (int32) the exercise dates;
         ``n_local``: the path count of ``data`` when it is not this backend's
-        shard (out-of-sample paths; ``stats`` then has ``pnl_wgs(n_local)`` rows)."""
+        shard (out-of-sample paths; ``stats`` then has ``pnl_wgs(n_local)`` rows).
+
+        ``costs``: the scan under transaction costs and a no-trade band instead
+        (one k_hedge_pnl_cost launch; None: the plain launch above): ``cost_stats``
+        is its ``[pnl_wgs, COST_NSTAT]`` float64 slab, ``cost_out`` / ``turn_out``
+        (float32) and ``trades_out`` (int32) the optional per-path cost carried
+        to the horizon, turnover and trade dates.  Not with ``exercise``."""
         nl = self.n_local if n_local is None else int(n_local)
         if nl != int(data.payoff.numel()):
             raise ValueError(f"pnl over {data.payoff.numel()} paths with n_local {nl}")
@@ -757,7 +765,31 @@ class HipBackend(StateBlocks):
             assert tau_out.dtype == torch.int32 and tau_out.numel() == nl
             d.tau_out = tau_out.data_ptr()
         assert stats.shape[0] == d.num_wgs and snap.shape[0] >= data.n_dates
-        n.pnl(d, self.stream)
+        if costs is None:
+            if any(t is not None for t in (cost_stats, cost_out, turn_out, trades_out)):
+                raise ValueError("pnl: cost outputs without costs")
+            n.pnl(d, self.stream)
+            return
+        if exercise is not None:
+            raise ValueError("pnl: costs with exercise (early exercise with costs is not supported)")
+        cd = n.CostPnlDesc()
+        cd.p = d
+        self._cost_terms(cd.c, "pnl", costs, nl, d.num_wgs, cost_stats, cost_out, turn_out, trades_out)
+        n.pnl_cost(cd, self.stream)
+
+    def _cost_terms(self, c, who, costs: Costs, nl: int, wgs: int, cost_stats, cost_out, turn_out, trades_out):
+        """Fill the ``CostTerms`` of a scan over ``nl`` paths on ``wgs`` workgroups."""
+        if (cost_stats is None or cost_stats.dtype != torch.float64 or cost_stats.dim() != 2
+                or tuple(cost_stats.shape) != (wgs, LC.COST_NSTAT)):
+            raise ValueError(f"{who}: cost_stats must be float64 [{wgs}, {LC.COST_NSTAT}]")
+        for name, t, dt in (("cost_out", cost_out, torch.float32), ("turn_out", turn_out, torch.float32),
+                            ("trades_out", trades_out, torch.int32)):
+            if t is not None and (t.dtype != dt or t.numel() != nl):
+                raise ValueError(f"{who}: {name} must be {dt} [{nl}]")
+        c.cost_rate, c.band, c.unwind = float(costs.rate), float(costs.band), 1 if costs.unwind else 0
+        n = self.native
+        c.cost_out, c.turn_out, c.trades_out = n.ptr(cost_out), n.ptr(turn_out), n.ptr(trades_out)
+        c.cstats = cost_stats.data_ptr()
 
     def oos_wgs(self, n_local: int) -> int:
         """Grid of a k_hedge_oos launch over ``n_local`` paths: persistent
@@ -765,13 +797,16 @@ class HipBackend(StateBlocks):
         return int(max(1, min(self.native.oos_max_wgs(), (int(n_local) + 255) // 256)))
 
     def oos(self, sim, snap, data: PnlData, stats, payoff_kind: int, strike: float, has_b: bool = False,
-            hold_c: float = 0.0, pnl_out=None, payoff_out=None):
+            hold_c: float = 0.0, pnl_out=None, payoff_out=None, costs: Costs | None = None, cost_stats=None,
+            cost_out=None, turn_out=None, trades_out=None):
         """Enqueue the fused simulate-and-hedge of fresh paths (one k_hedge_oos
         launch).  ``sim``: the scan's ``SimDesc`` (``ops.paths.gbm_desc`` /
         ``sv_desc``; its output pointers are the optional trace); ``data``: the
         run's standardisation and bond tables and the scalar ``wealth0`` (its
         path tables are not read); ``stats``: ``[num_wgs, EVAL_NSTAT]`` float64 -
-        its row count is the grid (``oos_wgs``, or fewer to make workgroups loop)."""
+        its row count is the grid (``oos_wgs``, or fewer to make workgroups loop).
+        ``costs`` and the cost outputs: as in :meth:`pnl` (one k_hedge_oos_cost
+        launch; ``cost_stats`` has the rows of ``stats``)."""
         n = self.native
         d = n.OosDesc()
         d.sim = sim
@@ -790,8 +825,16 @@ class HipBackend(StateBlocks):
         d.nin, d.h, d.nout, d.head = self.shape
         if snap.shape[0] < data.n_dates or data.fmu.shape[0] < data.n_dates or data.bond.numel() < data.n_dates + 1:
             raise ValueError("oos: snapshot / standardisation / bond tables shorter than n_dates")
-        n.oos(d, self.stream)
-        return d
+        if costs is None:
+            if any(t is not None for t in (cost_stats, cost_out, turn_out, trades_out)):
+                raise ValueError("oos: cost outputs without costs")
+            n.oos(d, self.stream)
+            return d
+        cd = n.CostOosDesc()
+        cd.o = d
+        self._cost_terms(cd.c, "oos", costs, nl, d.num_wgs, cost_stats, cost_out, turn_out, trades_out)
+        n.oos_cost(cd, self.stream)
+        return cd
 
     def pnl_finish(self, acc, w0, payoff, carry: float, stats, pnl_out=None):
         """Enqueue k_pnl_finish after the eval of date 0 of a run whose evals

@@ -121,6 +121,11 @@ class StateBlocks:
     def new_pnl_stats(self):
         return torch.zeros(self.pnl_wgs(), L.EVAL_NSTAT, dtype=torch.float64, device=self.device)
 
+    def new_cost_stats(self):
+        from ..ops import layout_cost as LC
+
+        return torch.zeros(self.pnl_wgs(), LC.COST_NSTAT, dtype=torch.float64, device=self.device)
+
 
 class _Cache:
     def __init__(self):
@@ -154,3 +159,14 @@ def reduce_stats(stats: torch.Tensor, world: int = 1) -> np.ndarray:
     s = s.detach().cpu().numpy().copy()
     s[L.ES_RESMIN], s[L.ES_RESMAX] = float(mn), float(mx)
     return s
+
+
+def reduce_cost_stats(slab: torch.Tensor, world: int = 1) -> np.ndarray:
+    """Sum the per-workgroup cost partials of a scan under transaction costs
+    (and across ranks) -> [COST_NSTAT] float64 (rows ``layout_cost.CS_*``)."""
+    s = slab.sum(dim=0)
+    if world > 1:
+        from ..parallel.dist import all_reduce_
+
+        all_reduce_(s)
+    return s.detach().cpu().numpy().copy()

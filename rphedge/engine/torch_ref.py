@@ -8,8 +8,9 @@ import torch
 
 from ..models.hedge_mlp import NetSpec, torch_forward
 from ..ops import layout as L
+from ..ops import layout_cost as LC
 from . import lm_ref
-from .config import DateData, Exercise, FitConfig, PnlData, TrainConfig
+from .config import Costs, DateData, Exercise, FitConfig, PnlData, TrainConfig
 from .lm_geometry import _lm_bias_index
 from .state import (StateBlocks, _check_eval_data, _normalise, _steps, current_copy, design, fit_template,
                     store_weights, with_bond)
@@ -181,9 +182,19 @@ class TorchBackend(StateBlocks):
         return 1
 
     def pnl(self, snap, data: PnlData, stats, has_b: bool = False, hold_c: float = 0.0, pnl_out=None,
-            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None):
+            exercise: Exercise | None = None, tau_out=None, n_local: int | None = None,
+            costs: Costs | None = None, cost_stats=None, cost_out=None, turn_out=None, trades_out=None):
         """Self-financing P&L scan (reference semantics of k_hedge_pnl;
-        ``n_local``: accepted like HipBackend.pnl's, the path count is the data's)."""
+        ``n_local``: accepted like HipBackend.pnl's, the path count is the data's).
+
+        ``costs``: under proportional transaction costs and a no-trade band
+        (reference semantics of k_hedge_pnl_cost, fp32 in its operation order;
+        csrc/rph_types.h CostTerms): per asset the held position follows the
+        target where ``t == 0``, ``band == 0`` or ``|target - held| > band``;
+        date t's cost ``rate sum_a |dh_a| S_a,t`` leaves the wealth before the
+        update.  ``cost_stats`` ([1, COST_NSTAT] float64) takes the sums,
+        ``cost_out`` / ``turn_out`` / ``trades_out`` the per-path cost carried
+        to the horizon, turnover and trade dates (t >= 1)."""
         spec, dt, P = self.spec, torch.float32, self.spec.nparams
         bond = data.bond.detach().cpu().double().numpy()
         fmu, fisd = data.fmu.detach().cpu(), data.fisd.detach().cpu()
@@ -196,6 +207,17 @@ class TorchBackend(StateBlocks):
             raise ValueError("pnl: has_b with exercise (early exercise takes one network)")
         if exercise is None and tau_out is not None:
             raise ValueError("pnl: tau_out without exercise")
+        if costs is None and any(t is not None for t in (cost_stats, cost_out, turn_out, trades_out)):
+            raise ValueError("pnl: cost outputs without costs")
+        if costs is not None:
+            if exercise is not None:
+                raise ValueError("pnl: costs with exercise (early exercise with costs is not supported)")
+            if cost_stats is None:
+                raise ValueError("pnl: costs without cost_stats")
+            rate, band = (torch.tensor(float(v), dtype=dt) for v in (costs.rate, costs.band))
+            held = None
+            cost_T, turn = torch.zeros_like(wealth), torch.zeros_like(wealth)
+            trades = torch.zeros(wealth.shape, dtype=torch.int32, device=wealth.device)
         tau = torch.full(wealth.shape, nd, dtype=torch.int32, device=wealth.device)
         pnl_ex = torch.zeros_like(wealth)
         paid = torch.zeros(wealth.shape, dtype=torch.float64, device=wealth.device)
@@ -224,10 +246,37 @@ class TorchBackend(StateBlocks):
                     wealth = torch.where(ex, wealth * to_end, wealth)  # W_tau in the bank account to the horizon
                     tau = torch.where(ex, torch.full_like(tau, t), tau)
                     alive = tau == nd
+                if costs is not None:
+                    now = [s.to(dt) for s in data.prices(t)]
+                    na = len(now)
+                    target = hold[:, :na]
+                    if held is None:
+                        held = torch.zeros_like(target)
+                    tr = (target - held).abs() > band
+                    if t == 0 or float(band) == 0.0:
+                        tr = torch.ones_like(tr)
+                    new = torch.where(tr, target, held)
+                    dv = torch.zeros_like(wealth)
+                    for a in range(na):  # ascending a
+                        dv = dv + (new[:, a] - held[:, a]).abs() * now[a]
+                    c = rate * dv
+                    wealth = wealth - c
+                    cost_T = cost_T + c * float(np.float32(bond[nd] / bond[t]))
+                    turn = turn + dv
+                    if t > 0:
+                        trades = trades + tr.any(dim=1).to(torch.int32)
+                    held = new
+                    hold = torch.cat([new, hold[:, na:]], dim=1)
                 w = wealth * grow
                 for a, (s0, s1) in enumerate(zip(data.prices(t), data.prices(t + 1))):
                     w = w + hold[:, a] * (s1.to(dt) - s0.to(dt) * grow)
                 wealth = torch.where(alive, w, wealth) if exercise is not None else w
+            if costs is not None and costs.unwind:  # the final position is sold at the horizon
+                dv = torch.zeros_like(wealth)
+                for a, s in enumerate(data.prices(nd)):
+                    dv = dv + held[:, a].abs() * s.to(dt)
+                c = rate * dv
+                wealth, cost_T, turn = wealth - c, cost_T + c, turn + dv
             pnl = wealth - data.payoff.to(dt)
             if exercise is not None:
                 pnl = torch.where(tau < nd, pnl_ex, pnl)
@@ -241,6 +290,15 @@ class TorchBackend(StateBlocks):
             if exercise is not None:
                 st[L.ES_EXER], st[L.ES_EXVAL], st[L.ES_TAU] = (tau < nd).sum(), paid.sum(), tau.double().sum()
             stats[0].copy_(st)
+            if costs is not None:
+                for out, v in ((cost_out, cost_T), (turn_out, turn), (trades_out, trades)):
+                    if out is not None:
+                        out.copy_(v)
+                cs = torch.zeros(LC.COST_NSTAT, dtype=torch.float64)
+                cd = cost_T.double()
+                cs[LC.CS_COST], cs[LC.CS_COST2], cs[LC.CS_TURN] = cd.sum(), (cd * cd).sum(), turn.double().sum()
+                cs[LC.CS_TRADES], cs[LC.CS_COUNT] = trades.double().sum(), cd.numel()
+                cost_stats[0].copy_(cs)
 
     def eval(self, wts, data: DateData, stats, wts_b=None, g_base=None, blend_c=0.0, hold_c=0.0,
              v_out=None, hold_out=None, resid_out=None, pred1_out=None, snap_a=None, snap_b=None,

@@ -27,8 +27,9 @@ import numpy as np
 import torch
 
 from . import risk
-from .engine import PnlData, reduce_stats
+from .engine import Costs, PnlData, reduce_cost_stats, reduce_stats
 from .ops import layout as L
+from .ops import layout_cost as LC
 from .ops import paths as P
 from .parallel import dist as D
 
@@ -100,6 +101,8 @@ class OosResult:
     mean_exercise_date: float | None = None
     policy_value: float | None = None
     stats: np.ndarray | None = None   # the summed statistics row (ES_* layout)
+    # the same paths under transaction costs (the keys of RunResult.costs; "in_sample": the run's own cost scan)
+    costs: dict | None = None
     seconds: float = 0.0
     chunks: int = 1
     extra: dict = field(default_factory=dict)
@@ -107,7 +110,7 @@ class OosResult:
     def as_dict(self) -> dict:
         d = {k: getattr(self, k) for k in ("mean", "std", "min", "max", "mean_terminal_wealth", "n_paths", "seed",
                                              "offset", "stress", "route", "in_sample", "std_ratio", "quantiles",
-                                             "exercise_share", "mean_exercise_date", "policy_value")}
+                                             "exercise_share", "mean_exercise_date", "policy_value", "costs")}
         return {k: v for k, v in d.items() if v is not None or k in ("stress", "in_sample", "std_ratio")}
 
 
@@ -151,6 +154,17 @@ def _in_sample(run, scale: float) -> dict | None:
     return {"mean": d.residual_mean * scale, "std": d.residual_std * scale,
             "min": float(d.stats[L.ES_RESMIN]) * scale, "max": float(d.stats[L.ES_RESMAX]) * scale,
             "mean_terminal_wealth": d.mean_value * scale}
+
+
+def _in_sample_costs(run, scale: float) -> dict | None:
+    """The run's own scan under its configured costs (None: it ran none)."""
+    from .driver import DateResult
+
+    ind = run.induction
+    if not getattr(ind, "pnl_done", False) or getattr(ind, "costs", None) is None:
+        return None
+    d = DateResult(index=-1, time=0.0, stats=reduce_stats(ind.cost_pnl_stats, run.di.world))
+    return run.cost_report(ind.costs, d, reduce_cost_stats(ind.cost_stats, run.di.world), None, fitted_v0(run) * scale)
 
 
 def _snapshots(run) -> torch.Tensor:
@@ -217,10 +231,37 @@ def _fused_scan(run, n: int, first: int, seeds: tuple, stress, trace: bool):
                             first, False, seeds[0], None, run.path_stat)
 
 
+def resolve_costs(run, costs) -> Costs | None:
+    """The costs of an out-of-sample test: None = the run's, False = off, a ``Costs`` or a dict of its fields."""
+    if costs is None:
+        k = run.costs
+    elif costs is False:
+        k = None
+    elif isinstance(costs, Costs):
+        k = costs
+    elif isinstance(costs, dict):
+        unknown = set(costs) - {"rate", "band", "unwind"}
+        if unknown or "rate" not in costs:
+            raise ValueError(f"costs dict takes rate, band, unwind (rate required), got {sorted(costs)}")
+        k = Costs(**costs)
+    else:
+        raise ValueError(f"costs must be None, False, an engine.Costs or a dict, got {costs!r}")
+    if k is not None and not k.active:
+        k = None
+    if k is not None and run.exercise is not None:
+        raise ValueError("out_of_sample: transaction costs with early exercise are not supported")
+    return k
+
+
 def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=None, keep_pnl=False,
-                  keep_paths=False, chunk_log2: int | None = None) -> OosResult:
+                  keep_paths=False, chunk_log2: int | None = None, costs=None, cost_only: bool = False) -> OosResult:
     """See :meth:`rphedge.api.HedgeRun.out_of_sample`.  ``chunk_log2``: the
-    materialised route's chunk (default ``OOS_CHUNK_LOG2``)."""
+    materialised route's chunk (default ``OOS_CHUNK_LOG2``).  ``cost_only``:
+    only the scan under ``costs`` runs (the frontier); the result's own
+    figures are then the net ones."""
+    costs = resolve_costs(run, costs)
+    if cost_only and costs is None:
+        raise ValueError("out_of_sample(cost_only=True) needs active costs")
     ind = run.induction
     if ind is None or not getattr(ind, "ran", None):
         raise RuntimeError("out_of_sample() needs a finished run: call run(), replay() or resume() first")
@@ -251,7 +292,7 @@ def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=
     be, dev, nd = run.backend, run.device, ind.n_dates
     has_b, hold_c, ex = bool(ind.cfg.q99), float(ind.hold_c), ind.cfg.exercise
     pnl = torch.empty(n_r, dtype=torch.float32, device=dev) if keep_pnl else None
-    kept, slabs = [], []
+    kept, slabs, nslabs, cslabs = [], [], [], []
     if use_fused:
         # one launch: nothing of size [dates, paths] exists unless the paths are asked for
         # (then the kernel's trace fills the buffers of a Paths object)
@@ -260,8 +301,16 @@ def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=
                        fisd=ind.pnl_data.fisd, w0=None, wealth0=v0, payoff=None)
         slab = torch.zeros(be.oos_wgs(n_r), L.EVAL_NSTAT, dtype=torch.float64, device=dev)
         kind, strike = payoff_code(run)
-        be.oos(sim, snap, data, slab, kind, strike, has_b=has_b, hold_c=hold_c, pnl_out=pnl)
-        slabs.append(slab)
+        if not cost_only:
+            be.oos(sim, snap, data, slab, kind, strike, has_b=has_b, hold_c=hold_c, pnl_out=pnl)
+            slabs.append(slab)
+        if costs is not None:
+            nslab = torch.zeros_like(slab)
+            cslab = torch.zeros(slab.shape[0], LC.COST_NSTAT, dtype=torch.float64, device=dev)
+            be.oos(sim, snap, data, nslab, kind, strike, has_b=has_b, hold_c=hold_c,
+                   pnl_out=pnl if cost_only else None, costs=costs, cost_stats=cslab)
+            nslabs.append(nslab)
+            cslabs.append(cslab)
         if keep_paths:
             kept.append(p)
     else:
@@ -274,16 +323,25 @@ def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=
                            payoff=run._payoff(p))
             slab = torch.zeros(be.pnl_wgs(n_c) if run.backend_kind == "hip" else 1, L.EVAL_NSTAT,
                                dtype=torch.float64, device=dev)
-            be.pnl(snap, data, slab, has_b=has_b, hold_c=hold_c, pnl_out=pnl[k0:k0 + n_c] if keep_pnl else None,
-                   exercise=ex, n_local=n_c)
-            slabs.append(slab)
+            pout = pnl[k0:k0 + n_c] if keep_pnl else None
+            if not cost_only:
+                be.pnl(snap, data, slab, has_b=has_b, hold_c=hold_c, pnl_out=pout, exercise=ex, n_local=n_c)
+                slabs.append(slab)
+            if costs is not None:
+                nslab = torch.zeros_like(slab)
+                cslab = torch.zeros(slab.shape[0], LC.COST_NSTAT, dtype=torch.float64, device=dev)
+                be.pnl(snap, data, nslab, has_b=has_b, hold_c=hold_c, pnl_out=pout if cost_only else None, n_local=n_c,
+                       costs=costs, cost_stats=cslab)
+                nslabs.append(nslab)
+                cslabs.append(cslab)
             if keep_paths:
                 kept.append(p)
             elif run.device.type == "cuda":
                 torch.cuda.synchronize(run.device)
             del p, data  # (without keep_paths the chunk's tables are released before the next is simulated)
     # the statistics rows of every chunk (and rank), summed the way collect() sums the in-sample ones
-    st = reduce_stats(torch.cat(slabs, dim=0), world)
+    nst = reduce_stats(torch.cat(nslabs, dim=0), world) if costs is not None else None
+    st = nst if cost_only else reduce_stats(torch.cat(slabs, dim=0), world)
     n = float(st[L.ES_COUNT])
     assert n == float(n_total), (n, n_total)
     m = st[L.ES_RES] / n
@@ -291,7 +349,15 @@ def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=
     res = OosResult(mean=float(m) * scale, std=std * scale, min=float(st[L.ES_RESMIN]) * scale,
                     max=float(st[L.ES_RESMAX]) * scale, mean_terminal_wealth=float(st[L.ES_V] / n) * scale,
                     n_paths=n_total, seed=seed, offset=offset, stress=stress,
-                    route="fused" if use_fused else "materialised", stats=st, chunks=len(slabs))
+                    route="fused" if use_fused else "materialised", stats=st, chunks=max(len(slabs), len(nslabs)))
+    if costs is not None:
+        from .driver import DateResult
+
+        cst = reduce_cost_stats(torch.cat(cslabs, dim=0), world)
+        assert float(cst[LC.CS_COUNT]) == float(n_total), (cst[LC.CS_COUNT], n_total)
+        res.costs = run.cost_report(costs, DateResult(index=-1, time=0.0, stats=nst), cst,
+                                    None if cost_only else res.std, v0 * scale)
+        res.costs["in_sample"] = _in_sample_costs(run, scale)
     res.in_sample = _in_sample(run, scale)
     if res.in_sample is not None and res.in_sample["std"] > 0:
         res.std_ratio = res.std / res.in_sample["std"]

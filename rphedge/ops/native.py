@@ -18,6 +18,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must be loaded before librphedge.so)
 
 from . import layout as L
+from . import layout_cost as LC
 from .layout import DP_SLOTS, MAXHOLD, MAXIN  # noqa: F401  (imported from here by the engine and the tests)
 
 # RPH_NATIVE_LIB=debug|asan selects the variant built by `python -m rphedge.build --debug|--asan`;
@@ -177,6 +178,28 @@ class SimRideDesc(C.Structure):
     ]
 
 
+class CostTerms(C.Structure):
+    """Proportional transaction costs and the no-trade band of a forward scan
+    (csrc/rph_types.h); ``cstats``: ``[num_wgs, COST_NSTAT]`` float64."""
+
+    _fields_ = [
+        ("cost_rate", C.c_float), ("band", C.c_float), ("unwind", C.c_int), ("pad", C.c_int),
+        ("cost_out", VP), ("turn_out", VP), ("trades_out", VP), ("cstats", VP),
+    ]
+
+
+class CostPnlDesc(C.Structure):
+    """k_hedge_pnl_cost (csrc/hedge_cost.hip): the P&L scan ``p`` under the costs ``c``."""
+
+    _fields_ = [("p", PnlDesc), ("c", CostTerms)]
+
+
+class CostOosDesc(C.Structure):
+    """k_hedge_oos_cost (csrc/hedge_oos.hip): the fused simulate-and-hedge ``o`` under the costs ``c``."""
+
+    _fields_ = [("o", OosDesc), ("c", CostTerms)]
+
+
 DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, SimDesc)
 # descriptors of the native library's second field table (csrc/rph_layout.h
 # RPH_DESCRIPTORS_EXT, rph_layout_fields_ext): checked by name at load like the first
@@ -185,6 +208,11 @@ DESCRIPTORS_EXT = (OosDesc,)
 DESCRIPTORS_RIDE = (SelfTargetDesc,)
 # ... and its fourth (RPH_DESCRIPTORS_SIM, rph_layout_fields_sim): the sim ride
 DESCRIPTORS_SIM = (SimRideDesc,)
+
+# ... and its fifth (RPH_DESCRIPTORS_COST, rph_layout_fields_cost): the scans under
+# transaction costs; the table also holds the rows of the embedded CostTerms,
+# and has constants of its own (rph_layout_consts_cost, ops/layout_cost.py)
+DESCRIPTORS_COST = (CostPnlDesc, CostOosDesc)
 
 # upper-case ints of layout.py that the native table does not hold (Python only)
 PYTHON_ONLY: tuple[str, ...] = ()
@@ -228,6 +256,15 @@ def native_layout_sim(lib) -> list[tuple[str, str, int, int]]:
     return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
 
 
+def native_layout_cost(lib) -> tuple[list[tuple[str, str, int, int]], list[tuple[str, int]]]:
+    """The library's fifth field table, the rows of :data:`DESCRIPTORS_COST` and
+    of ``CostTerms``, and the constants of ``ops/layout_cost.py``."""
+    fr, cr = C.POINTER(_FieldRow)(), C.POINTER(_ConstRow)()
+    nf, nc = lib.rph_layout_fields_cost(C.byref(fr)), lib.rph_layout_consts_cost(C.byref(cr))
+    return ([(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]],
+            [(r.name.decode(), r.value) for r in cr[:nc]])
+
+
 def layout_mismatches(fields, consts, classes=DESCRIPTORS, layout=L) -> list[str]:
     """Every difference between the native tables (:func:`native_layout`) and
     the Python mirrors: the ctypes ``classes`` field by field (offset and size
@@ -260,6 +297,12 @@ def _bind(lib):
         "rph_layout_fields_ext": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_fields_ride": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_fields_sim": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_layout_fields_cost": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_layout_consts_cost": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
+        "rph_pnl_cost": (C.c_int, [C.POINTER(CostPnlDesc), VP]),
+        "rph_pnl_cost_check": (C.c_int, [C.POINTER(CostPnlDesc)]),
+        "rph_oos_cost": (C.c_int, [C.POINTER(CostOosDesc), VP]),
+        "rph_oos_cost_check": (C.c_int, [C.POINTER(CostOosDesc)]),
         "rph_sim_ride_slice": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2),
         "rph_sim_ride_head": (C.c_int, [C.POINTER(SimRideDesc), C.POINTER(SimDesc), VP]),
         "rph_sim_ride_rest": (C.c_int, [C.POINTER(SimRideDesc), C.c_int, VP]),
@@ -352,6 +395,8 @@ def load(required: bool | None = None):
         fields, consts = native_layout(lib)
         bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib) + native_layout_sim(lib),
                                 consts, classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE + DESCRIPTORS_SIM)
+        cfields, cconsts = native_layout_cost(lib)
+        bad += layout_mismatches(cfields, cconsts, classes=(CostTerms,) + DESCRIPTORS_COST, layout=LC)
         if bad:
             raise RuntimeError("native/Python layout mismatch:\n  " + "\n  ".join(bad))
         _lib = lib
@@ -606,6 +651,30 @@ def pnl(desc: PnlDesc, stream=None):
     """Self-financing hedge P&L scan over the rebalancing dates (k_hedge_pnl)."""
     load(required=True)
     _check(_lib.rph_pnl(C.byref(desc), stream_handle(stream)), "rph_pnl")
+
+
+def pnl_cost(desc: CostPnlDesc, stream=None):
+    """The P&L scan under transaction costs and a no-trade band (k_hedge_pnl_cost)."""
+    load(required=True)
+    _check(_lib.rph_pnl_cost(C.byref(desc), stream_handle(stream)), "rph_pnl_cost")
+
+
+def pnl_cost_check(desc: CostPnlDesc):
+    """The descriptor checks of :func:`pnl_cost` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_pnl_cost_check(C.byref(desc)), "rph_pnl_cost")
+
+
+def oos_cost(desc: CostOosDesc, stream=None):
+    """Fused simulate-and-hedge of fresh paths under transaction costs (k_hedge_oos_cost)."""
+    load(required=True)
+    _check(_lib.rph_oos_cost(C.byref(desc), stream_handle(stream)), "rph_oos_cost")
+
+
+def oos_cost_check(desc: CostOosDesc):
+    """The descriptor checks of :func:`oos_cost` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_oos_cost_check(C.byref(desc)), "rph_oos_cost")
 
 
 def oos(desc: OosDesc, stream=None):

@@ -104,6 +104,32 @@ def exercise_boundary(res) -> dict:
             "tree": [tree[t] for t in dates] if tree is not None else None}
 
 
+def cost_frontier_table(rows) -> str:
+    """The rows of ``HedgeRun.cost_frontier`` as a text table: band, mean cost,
+    net P&L std and mean, trades per path."""
+    head = f"{'band':>8} {'mean cost':>11} {'net P&L std':>12} {'net P&L mean':>13} {'trades/path':>12}"
+    lines = [head, "-" * len(head)]
+    for r in rows:
+        lines.append(f"{r['band']:8.4g} {r['mean_cost']:11.5f} {r['net_pnl_std']:12.5f} {r['net_pnl_mean']:13.5f} "
+                     f"{r['trades_per_path']:12.3f}")
+    return "\n".join(lines)
+
+
+def plot_cost_frontier(rows, out_prefix: str = "rphedge") -> list:
+    """Mean cost against net P&L std over the no-trade bands of ``HedgeRun.cost_frontier``."""
+    plt = _plt()
+    files = []
+    fig, ax = plt.subplots()
+    ax.plot([r["mean_cost"] for r in rows], [r["net_pnl_std"] for r in rows], "o-")
+    for r in rows:
+        ax.annotate(f"band {r['band']:g}", (r["mean_cost"], r["net_pnl_std"]), textcoords="offset points", xytext=(6, 6))
+    ax.set_xlabel("mean transaction cost (at the horizon)")
+    ax.set_ylabel("net P&L std")
+    ax.set_title("No-trade band: cost against risk")
+    _save(plt, fig, files, f"{out_prefix}_cost_frontier.png")
+    return files
+
+
 def _plt():
     """matplotlib with the reference notebooks' style (C43: bmh, 20x7, font 13)."""
     import matplotlib

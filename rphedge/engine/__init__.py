@@ -38,7 +38,8 @@ from ..ops.native import MAXIN  # noqa: F401
 from .config import (Costs, DateData, Exercise, FitConfig, PnlData, TrainConfig, fit_seed, geometric_lr_schedule,  # noqa: F401
                      keras_lr_schedule, pnl_fold_factors)
 from .lm_geometry import (GRAM_BLOCKS, _lm_bias_index, _lm_out_n, gram_subsample, lm_gram_geometry,  # noqa: F401
-                          lm_og_wgs, lm_out_gram, lm_out_nu, lm_pass_schedule, lm_pass_wgs, lm_tpack_image, lm_tpack_len)
+                          lm_gram_red_wgs, lm_og_wgs, lm_out_gram, lm_out_nu, lm_pass_blocks, lm_pass_schedule,
+                          lm_pass_wgs, lm_pk_red_wgs, lm_reduce_trees, lm_tpack_image, lm_tpack_len)
 from .state import (_normalise, current_weights, fit_summary, fit_template, make_opt, make_weights,  # noqa: F401
                     reduce_cost_stats, reduce_stats, set_weights)
 from .torch_ref import TorchBackend

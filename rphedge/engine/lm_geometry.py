@@ -96,6 +96,67 @@ def lm_pass_schedule(n_local: int, leaf_paths: int = 0, wps: int = 1) -> tuple[i
     return nw, int(-(-nblk // (4 * nw)))
 
 
+def lm_pass_blocks(batch: int, num_wgs: int, gram_wgs: int, gram_skip: int, leaf_blocks: int = 0):
+    """(regime, blocks): the 128-path blocks of every wave of an LM pass over
+    ``batch`` paths (csrc/hedge_narrow.h NarrowPairBody::sched, line by line);
+    ``blocks[w]`` lists the blocks of wave ``w`` = 4 x workgroup + wave, in the
+    order the wave runs them.  ``gram_wgs`` is what k_lm_pass hands the
+    schedule: 0 with Gram-only workgroups after the path grid (LmDesc.gram_base
+    > 0) and in a final evaluation.  Regimes: "leaf" (contiguous leaves),
+    "cyclic", and "split" - the waves of the Gram workgroups take gram_skip
+    blocks fewer than an even split (``gb`` each, possibly none), the others
+    share the rest."""
+    nblk = (int(batch) + 127) // 128
+    TW = int(num_wgs) * 4
+    if leaf_blocks > 0:
+        out = []
+        for w in range(TW):
+            b0 = w * leaf_blocks
+            b1 = b0 + leaf_blocks
+            out.append(list(range(b0, b1 if b1 < nblk else nblk)))
+        return "leaf", out
+    GW = (gram_wgs if gram_wgs < num_wgs else num_wgs) * 4
+    per = nblk // TW
+    if gram_skip <= 0 or GW >= TW or per <= 0:
+        return "cyclic", [list(range(w, nblk, TW)) for w in range(TW)]
+    gb = per - gram_skip if per > gram_skip else 0
+    out = []
+    for w in range(TW):
+        if w < GW:
+            out.append(list(range(w, GW * gb, GW)))
+        else:
+            out.append(list(range(GW * gb + (w - GW), nblk, TW - GW)))
+    # (no Gram workgroup among the path workgroups: the second branch alone, which is the cyclic schedule)
+    return ("split" if GW > 0 else "cyclic"), out
+
+
+LM_TPE_MAX = 16   # csrc/hedge_lm.hip: Gram slabs / packet rows up to which k_lm_reduce sums an entry in one thread
+LM_PK_C_MAX = 32  # packet rows up to which a reduce workgroup takes 32 entries
+
+
+def lm_gram_red_wgs(ng: int, gram_wgs: int) -> int:
+    """Gram workgroups of k_lm_reduce over ``ng`` Gram entries (csrc/hedge_lm.hip
+    lm_gram_red_wgs): 1,024 entries each up to LM_TPE_MAX slabs, else 64."""
+    return ng // 1024 if gram_wgs <= LM_TPE_MAX else ng // 64
+
+
+def lm_pk_red_wgs(R: int, num_wgs: int, dp_fused: int = 0) -> int:
+    """Packet workgroups of k_lm_reduce (csrc/hedge_lm.hip lm_pk_red_wgs)."""
+    if dp_fused:
+        return R // 4
+    return 1 if num_wgs <= LM_TPE_MAX else R // 32 if num_wgs <= LM_PK_C_MAX else R // 4
+
+
+def lm_reduce_trees(R: int, num_wgs: int, gram_wgs: int) -> tuple[str, str]:
+    """(packet tree, Gram tree) k_lm_reduce runs without the fused exchange:
+    packet "one" (one workgroup, thread = entry), "r32" (32 entries per
+    workgroup), "r4" (4 entries, up to 256 rows) or "r4x2" (up to 512 rows, one
+    level deeper); Gram "thread" (thread = entry) or "lds"."""
+    npw = lm_pk_red_wgs(R, num_wgs)
+    pk = "one" if npw == 1 else "r32" if npw == R // 32 else "r4" if num_wgs <= 256 else "r4x2"
+    return pk, ("thread" if lm_gram_red_wgs(1024, gram_wgs) == 1 else "lds")
+
+
 def lm_tpack_len(P: int, nblk: int) -> int:
     """Doubles of the solve's tile-store image of the Gram that k_lm_reduce
     writes after the 32 x 32 blocks (csrc/hedge_lm.hip LmTPack: nets with up

@@ -51,10 +51,23 @@ def _pass0(be, d, lm, st=None):
     return {k: b[k].cpu().numpy().copy() for k in ("red", "slab_b", "slab_g")}
 
 
-def _both_routes(shape, n, sched, start):
+def _override(lm, n, over):
+    """The split block schedule at a few thousand paths: fewer path workgroups
+    and a Gram of the first 64 k paths, set on a prepared LmDesc (the buffers
+    are sized for the natural, larger geometry)."""
+    if over is None:
+        return
+    num_wgs, k, skip = over
+    assert num_wgs <= lm.num_wgs and k <= lm.gram_wgs and lm.leaf_blocks == 0 and lm.gram_base == 0
+    lm.num_wgs, lm.gram_skip = num_wgs, skip
+    lm.gram_wgs, lm.gram_blk, lm.gram_blk_stride, lm.inv_ns = k, 64 * k, n, 1.0 / (64 * k)
+
+
+def _both_routes(shape, n, sched, start, over=None):
     """(present route, self-target route): slabs, reduced block and the target
     array of pass 0.  ``start``: "same" = the start point IS the target net (one
-    NetWeights, the induction's case), "w0" = LmDesc.w0 names another start."""
+    NetWeights, the induction's case), "w0" = LmDesc.w0 names another start.
+    ``over``: (num_wgs, Gram workgroups, gram_skip) set on both routes' descriptors."""
     from rphedge.engine import FitConfig, HipBackend, TrainConfig
     from rphedge.ops import layout as L
 
@@ -75,12 +88,14 @@ def _both_routes(shape, n, sched, start):
     assert np.isfinite(y).all() and np.std(y) > 1e-3
     d, lm = be._lm_prepare(w, o, f, fit, fc)
     lm.w0 = w0.data_ptr() if start == "w0" else None
+    _override(lm, n, over)
     old = _pass0(be, d, lm)
     # self-target route: the target array starts as NaN, pass 0 fills it
     fit.target.fill_(float("nan"))
     d, lm, st = be._lm_prepare(w, o, f, fit, fc, ride=be.eval_desc(w, ev, stats))
     lm.w0 = w0.data_ptr() if start == "w0" else None
     assert st.st_out == fit.target.data_ptr() and st.st_wts == w.data_ptr()
+    _override(lm, n, over)
     new = _pass0(be, d, lm, st)
     y_st = fit.target.cpu().numpy().copy()
     lm.w0 = None
@@ -99,6 +114,30 @@ def test_self_target_pass_is_bytewise_the_present_pass(shape, n, sched):
     assert (leaf > 0) == (sched == "leaf") and nw > 1
     assert _same(y, y_st)  # the stored target IS the eval's v_out, every path written
     assert np.isfinite(old["slab_b"]).all() and np.count_nonzero(old["slab_b"]) > old["slab_b"].size // 4
+    for k in ("slab_b", "slab_g", "red"):
+        assert _same(old[k], new[k]), k
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_self_target_pass_is_bytewise_the_present_pass_on_the_split_schedule(shape):
+    """The third block schedule (NarrowPairBody::sched with per > gram_skip,
+    what a 2^20-path fit runs; tests/test_gpu_lm_geometry.py split5184): 5184
+    paths on 2 path workgroups, one Gram workgroup whose waves take 2 blocks
+    each, the others 9, 8, 8, 8 with the half-masked 41st block.  The same
+    byte-for-byte assertions; packet rows and Gram slabs past the overridden
+    grid keep their NaN fill on both routes."""
+    from rphedge.engine import lm_pass_blocks
+
+    n, over = 5184, (2, 1, 3)
+    regime, blocks = lm_pass_blocks(n, *over)
+    assert regime == "split" and [len(w) for w in blocks] == [2, 2, 2, 2, 9, 8, 8, 8]
+    old, new, y, y_st, nw, leaf = _both_routes(shape, n, "cyclic", "same", over)
+    assert leaf == 0 and nw == 2
+    assert _same(y, y_st)
+    live = old["slab_b"][:nw]
+    assert np.isfinite(live).all() and np.count_nonzero(live) > live.size // 4
+    assert np.isnan(old["slab_b"][nw:]).all() and np.isnan(old["slab_g"][1:]).all()
+    assert np.isfinite(old["slab_g"][0]).all()
     for k in ("slab_b", "slab_g", "red"):
         assert _same(old[k], new[k]), k
 

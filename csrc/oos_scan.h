@@ -34,13 +34,19 @@
 
 namespace rph {
 
+// MODEL = SIM_MERTON (k_hedge_oos_jump / k_hedge_oos_jump_cost): the Merton
+// step of k_sim_jump (JumpScan) with the jump terms `jt`; every jump term sits
+// behind `if constexpr (JUMP)`, and `jt` is unused otherwise.
 template <int NIN, int H, int NO, int HEAD, int MODEL, int STAT, bool ALIGNED, bool COST>
-__device__ __forceinline__ void oos_scan(const OosDesc& d, [[maybe_unused]] const CostTerms* ct) {
+__device__ __forceinline__ void oos_scan(const OosDesc& d, [[maybe_unused]] const CostTerms* ct,
+                                         [[maybe_unused]] const JumpTerms* jt = nullptr) {
   using S = NetShape<NIN, H, NO, HEAD>;
   constexpr int NHOLD = S::NHOLD;
   static_assert(NHOLD == 2, "one traded asset and the bank account");
   static_assert(NIN == ((STAT != STAT_NONE || MODEL == SIM_HESTON) ? 2 : 1), "features: S, or S and statistic / variance");
   constexpr bool SV = MODEL == SIM_HESTON;
+  constexpr bool JUMP = MODEL == SIM_MERTON;
+  static_assert(!JUMP || STAT == STAT_NONE, "the Merton scan has no path statistic");
   constexpr int WBOFF = (S::P + 3) / 4 * 4;
   RPH_DASSERT(d.sim.n_local > 0 && d.num_wgs == (int)gridDim.x && d.snap != nullptr && d.stats != nullptr);
   __shared__ __attribute__((aligned(16))) float wl[WBOFF + S::P + 4];
@@ -67,9 +73,11 @@ __device__ __forceinline__ void oos_scan(const OosDesc& d, [[maybe_unused]] cons
     const bool ok = p < n;
     const int pp = ok ? p : n - 1;  // past the end: a valid path, never stored or counted
     const uint32_t g = gray_code((uint64_t)sim_gidx(sd, pp));
-    GbmScan<float, SV ? SIM_GBM_LOG : MODEL, STAT> gs;
+    GbmScan<float, (SV || JUMP) ? SIM_GBM_LOG : MODEL, STAT> gs;
     SvScan<float, SIM_HESTON> ss;
+    [[maybe_unused]] JumpScan<float> js;
     if constexpr (SV) ss.init(sd);
+    else if constexpr (JUMP) js.init(sd, *jt);
     else gs.init(sd);
     // one fine step, as the scan takes it
     auto fine = [&](const int t) {
@@ -77,6 +85,14 @@ __device__ __forceinline__ void oos_scan(const OosDesc& d, [[maybe_unused]] cons
         const float z1 = ndtri_u30<float>(sobol_point<ALIGNED>(sd.sv1 + (size_t)t * 32, sd.shift1[t], g));
         const uint32_t x2 = sobol_point<ALIGNED>(sd.sv2 + (size_t)t * 32, sd.shift2[t], g);
         ss.step(sd, z1, x2);
+      } else if constexpr (JUMP) {
+        const size_t nf = (size_t)n_fine;
+        const float z = ndtri_u30<float>(sobol_point<ALIGNED>(sd.sv1 + (size_t)t * 32, sd.shift1[t], g));
+        const int nj = JumpScan<float>::count(*jt, sobol_point<ALIGNED>(sd.sv2 + (size_t)t * 32, sd.shift2[t], g));
+        float zeta = 0.f;
+        if (JumpScan<float>::jumps_in_wave(nj))
+          zeta = ndtri_u30<float>(sobol_point<ALIGNED>(sd.sv2 + (nf + (size_t)t) * 32, sd.shift2[nf + (size_t)t], g));
+        js.step(z, nj, zeta);
       } else {
         const float z = ndtri_u30<float>(sobol_point<ALIGNED>(sd.sv1 + (size_t)t * 32, sd.shift1[t], g));
         gs.step(z);
@@ -90,6 +106,9 @@ __device__ __forceinline__ void oos_scan(const OosDesc& d, [[maybe_unused]] cons
       if constexpr (SV) {
         s = (float)ss.price() * inv0;
         x = (float)ss.v;
+      } else if constexpr (JUMP) {
+        s = (float)js.price() * inv0;
+        x = s;
       } else {
         s = (float)gs.price() * inv0;
         x = (float)gs.stat * inv0;

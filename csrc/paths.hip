@@ -5,6 +5,7 @@
 //       optional running statistic of the fine GBM path (mean / geometric
 //       mean / max / min: Asian and lookback options)
 //   K4  SV scans (reference CIR-on-sigma RP:282-289; full-truncation Heston)
+//   K3b Merton jump-diffusion scan (k_sim_jump: log-Euler GBM + compound-Poisson jumps)
 //   K5+K6 mortality intensity Euler + binomial survivors (RP:71-84)
 //   K7  payoffs (guarantee RP:88/:184, call/put EO:328-329, basket call,
 //       floating strike)
@@ -63,6 +64,38 @@ __global__ __launch_bounds__(256) void k_sim_scan_pair(const SimDesc a, const Si
                                                        const SimPay pay) {
   if ((int)blockIdx.x < split) sim_scan_block<Real, ALIGNED, MODEL, STAT, WIDE>(a, (int)blockIdx.x, pay);
   else sim_scan_block<Real, ALIGNED, MODEL, STAT, WIDE>(b, (int)blockIdx.x - split);
+}
+
+// ---------------------------------------------------------------------------
+// Merton jump-diffusion scan (SIM_MERTON; JumpScan in sim_step.h): the stores,
+// the index map and the final value of the plain GBM scan.  Table 1 -> the
+// diffusion normals, table 2 -> the count uniform of step t at dimension t and
+// the jump-size normal at dimension n_fine + t.
+// ---------------------------------------------------------------------------
+template <typename Real, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_sim_jump(const SimDesc d, const JumpTerms j) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (!ALIGNED && p >= d.n_local) return;
+  const uint32_t g = gray_code((uint64_t)sim_gidx(d, p));
+  const float inv0 = (float)d.inv_norm[0];
+  const size_t n = (size_t)d.n_local;
+  const size_t nf = (size_t)d.n_fine;
+  JumpScan<Real> js;
+  js.init(d, j);
+  d.out[p] = (float)d.s0[0] * inv0;
+  for (int t = 1; t < d.n_fine; ++t) {
+    const Real z = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv1 + (size_t)t * 32, d.shift1[t], g));
+    const int nj = JumpScan<Real>::count(j, sobol_point<ALIGNED>(d.sv2 + (size_t)t * 32, d.shift2[t], g));
+    Real zeta = (Real)0;
+    if (JumpScan<Real>::jumps_in_wave(nj))
+      zeta = ndtri_u30<Real>(sobol_point<ALIGNED>(d.sv2 + (nf + (size_t)t) * 32, d.shift2[nf + (size_t)t], g));
+    js.step(z, nj, zeta);
+    if (t % d.reduction == 0) {
+      const int c = t / d.reduction;
+      if (c < d.n_coarse) d.out[(size_t)c * n + p] = (float)js.price() * inv0;
+    }
+  }
+  if (d.final_out) d.final_out[p] = (float)js.price() * inv0;
 }
 
 // ---------------------------------------------------------------------------
@@ -317,10 +350,42 @@ static bool sim_aligned(const SimDesc* d) {
 extern "C" int rph_simulate(const SimDesc* d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (int rc = validate_sim(d, "rph_simulate")) return rc;
+  if (d->model == SIM_MERTON) return rph_report("rph_simulate", "SIM_MERTON scans take their JumpTerms through rph_simulate_jump");
   const bool aligned = sim_aligned(d);
   if (d->model == SIM_BASKET) return aligned ? launch_basket<true>(d, s) : launch_basket<false>(d, s);
   if (d->fp64) return aligned ? launch_scan<double, true>(d, s) : launch_scan<double, false>(d, s);
   return aligned ? launch_scan<float, true>(d, s) : launch_scan<float, false>(d, s);
+}
+
+// The Merton jump-diffusion scan (k_sim_jump): rph_simulate's checks, then the jump terms' and the tables'.
+static int validate_sim_jump(const SimDesc* d, const JumpTerms* j, const char* who) {
+  if (d->model != SIM_MERTON) return rph_report(who, "model must be SIM_MERTON");
+  if (int rc = validate_sim(d, who)) return rc;
+  if (d->na != 1) return rph_report(who, "SIM_MERTON simulates one asset");
+  if (int rc = validate_jump(who, *d, j)) return rc;
+  if (d->n_local > 0 && !d->out) return rph_report(who, "null out buffer");
+  return 0;
+}
+
+// The checks of rph_simulate_jump without the launch.
+extern "C" int rph_simulate_jump_check(const SimDesc* d, const JumpTerms* j) {
+  return validate_sim_jump(d, j, "rph_simulate_jump");
+}
+
+extern "C" int rph_simulate_jump(const SimDesc* d, const JumpTerms* j, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = validate_sim_jump(d, j, "rph_simulate_jump")) return rc;
+  if (d->n_local <= 0) return 0;
+  const dim3 grid(grid_for(d->n_local)), block(256);
+  const bool aligned = sim_aligned(d);
+  if (d->fp64) {
+    if (aligned) hipLaunchKernelGGL((k_sim_jump<double, true>), grid, block, 0, s, *d, *j);
+    else hipLaunchKernelGGL((k_sim_jump<double, false>), grid, block, 0, s, *d, *j);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_sim_jump<float, true>), grid, block, 0, s, *d, *j);
+    else hipLaunchKernelGGL((k_sim_jump<float, false>), grid, block, 0, s, *d, *j);
+  }
+  return (int)hipGetLastError();
 }
 
 // Scans a and b (independent outputs) in ONE launch when both select the same

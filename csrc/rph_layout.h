@@ -64,6 +64,7 @@ namespace rph {
 
 #define RPH_FIELDS_CostTerms(X, T) \
   X(T, cost_rate) X(T, band) X(T, unwind) X(T, pad) X(T, cost_out) X(T, turn_out) X(T, trades_out) X(T, cstats)
+#define RPH_FIELDS_JumpTerms(X, T) X(T, lam) X(T, mu_j) X(T, sig_j) X(T, thr)
 #define RPH_FIELDS_CostPnlDesc(X, T) X(T, p) X(T, c)
 #define RPH_FIELDS_CostOosDesc(X, T) X(T, o) X(T, c)
 
@@ -78,6 +79,8 @@ namespace rph {
 #define RPH_DESCRIPTORS_SIM(X) X(SimRideDesc)
 // ... and of the scans under transaction costs (rph_layout_fields_cost; native.py DESCRIPTORS_COST)
 #define RPH_DESCRIPTORS_COST(X) X(CostTerms) X(CostPnlDesc) X(CostOosDesc)
+// ... and of the Merton jump scans (rph_layout_fields_jump; native.py DESCRIPTORS_JUMP)
+#define RPH_DESCRIPTORS_JUMP(X) X(JumpTerms)
 
 struct FieldRow {
   const char* strct;
@@ -92,6 +95,7 @@ constexpr FieldRow kFieldRowsExt[] = {RPH_DESCRIPTORS_EXT(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsRide[] = {RPH_DESCRIPTORS_RIDE(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsSim[] = {RPH_DESCRIPTORS_SIM(RPH_STRUCT_ROWS)};
 constexpr FieldRow kFieldRowsCost[] = {RPH_DESCRIPTORS_COST(RPH_STRUCT_ROWS)};
+constexpr FieldRow kFieldRowsJump[] = {RPH_DESCRIPTORS_JUMP(RPH_STRUCT_ROWS)};
 
 // The listed fields of `strct` start at 0, follow each other with no gap and
 // end at `size`: with no implicit padding in the struct, none is left out.
@@ -118,11 +122,13 @@ constexpr bool layout_covers(const FieldRow (&rows)[N], const char* strct, size_
 #define RPH_STRUCT_COVERED_RIDE(T) RPH_STRUCT_COVERED_IN(kFieldRowsRide, T)
 #define RPH_STRUCT_COVERED_SIM(T) RPH_STRUCT_COVERED_IN(kFieldRowsSim, T)
 #define RPH_STRUCT_COVERED_COST(T) RPH_STRUCT_COVERED_IN(kFieldRowsCost, T)
+#define RPH_STRUCT_COVERED_JUMP(T) RPH_STRUCT_COVERED_IN(kFieldRowsJump, T)
 RPH_DESCRIPTORS(RPH_STRUCT_COVERED)
 RPH_DESCRIPTORS_EXT(RPH_STRUCT_COVERED_EXT)
 RPH_DESCRIPTORS_RIDE(RPH_STRUCT_COVERED_RIDE)
 RPH_DESCRIPTORS_SIM(RPH_STRUCT_COVERED_SIM)
 RPH_DESCRIPTORS_COST(RPH_STRUCT_COVERED_COST)
+RPH_DESCRIPTORS_JUMP(RPH_STRUCT_COVERED_JUMP)
 
 // Constants, by their names in rphedge/ops/layout.py.
 struct ConstRow {
@@ -145,7 +151,7 @@ constexpr ConstRow kConstRows[] = {
     RPH_CONST(EX_NONE) RPH_CONST(EX_PUT) RPH_CONST(EX_CALL) RPH_CONST(HESTON_EULER) RPH_CONST(HESTON_QE)
     RPH_CONST(STAT_NONE) RPH_CONST(STAT_MEAN) RPH_CONST(STAT_GEOMEAN) RPH_CONST(STAT_MAX) RPH_CONST(STAT_MIN)
     RPH_CONST(SIM_GBM_ARITH) RPH_CONST(SIM_GBM_LOG) RPH_CONST(SIM_SV_REF) RPH_CONST(SIM_HESTON) RPH_CONST(SIM_BASKET)
-    RPH_CONST(SIM_MORTALITY)
+    RPH_CONST(SIM_MORTALITY) RPH_CONST(SIM_MERTON) RPH_CONST(JUMP_MAX)
     // EvalStat
     RPH_CONST(ES_V) RPH_CONST(ES_V2) RPH_CONST(ES_RES) RPH_CONST(ES_RES2) RPH_CONST(ES_ABSRES) RPH_CONST(ES_APE)
     RPH_CONST(ES_PRED1) RPH_CONST(ES_COUNT) RPH_CONST(ES_HOLD) RPH_CONST(ES_HOLD2) RPH_CONST(ES_RESMIN)

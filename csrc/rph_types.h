@@ -627,6 +627,25 @@ enum SimModel : int {
   SIM_HESTON = 3,      // full-truncation Heston, rho-correlated
   SIM_BASKET = 4,      // correlated log-GBM basket (Cholesky)
   SIM_MORTALITY = 5,   // lambda Euler + binomial survivors             (RP:71-84)
+  SIM_MERTON = 6,      // log-Euler GBM + compound-Poisson log-normal jumps (JumpTerms; k_sim_jump)
+};
+
+// Merton jump-diffusion (SIM_MERTON): the jump terms of a scan, a second
+// by-value kernel argument beside SimDesc (k_sim_jump, k_hedge_oos_jump).  Per
+// fine step t >= 1, after the SIM_GBM_LOG update with the compensated drift
+// (mu - sigma^2/2 - lam kappa) dt, kappa = exp(mu_j + sig_j^2/2) - 1:
+//   N_t = #{k < JUMP_MAX : u >= thr[k]},  u the step's raw 30-bit count uniform
+//   if N_t > 0:  log S += N_t mu_j + sqrt(N_t) sig_j zeta_t
+// thr[k] = min(floor(F_k 2^30), 2^30), F_k the Poisson(lam dt) CDF in fp64 on
+// the host (ops/paths.py merton_thresholds): the count is an integer
+// comparison, the same on the device and in the numpy twin.  Tables: sv1 the
+// diffusion normals [n_fine]; sv2 the count uniforms [0, n_fine) and the
+// jump-size normals [n_fine, 2 n_fine) (dims2 >= 2 n_fine).
+constexpr int JUMP_MAX = 8;    // jumps per fine step at most
+struct JumpTerms {
+  double lam;                    // intensity per year (>= 0)
+  double mu_j, sig_j;            // mean and std of the log jump size
+  uint32_t thr[JUMP_MAX];        // non-decreasing count thresholds, each <= 2^30
 };
 
 }  // namespace rph

@@ -73,6 +73,11 @@ extern "C" int rph_layout_fields_cost(const FieldRow** rows) {
   return (int)(sizeof(kFieldRowsCost) / sizeof(kFieldRowsCost[0]));
 }
 
+extern "C" int rph_layout_fields_jump(const FieldRow** rows) {
+  *rows = kFieldRowsJump;
+  return (int)(sizeof(kFieldRowsJump) / sizeof(kFieldRowsJump[0]));
+}
+
 extern "C" int rph_layout_consts_cost(const ConstRow** rows) {
   *rows = kConstRowsCost;
   return (int)(sizeof(kConstRowsCost) / sizeof(kConstRowsCost[0]));

@@ -1,13 +1,15 @@
 // rphedge — the per-step code of the single-asset path scans, shared by the
-// scans that store paths (paths.hip: k_sim_scan / k_sim_scan_pair) and the
-// fused simulate-and-hedge kernel (hedge_oos.hip: k_hedge_oos), so both walk a
+// scans that store paths (paths.hip: k_sim_scan / k_sim_scan_pair / k_sim_jump)
+// and the fused simulate-and-hedge kernels (hedge_oos.hip), so both walk a
 // path through the same operations in the same order:
 //   GbmScan  arithmetic Euler (RP:64-65) / log-Euler (EO:161-165) GBM with the
 //            optional running statistic of the fine path
 //   SvScan   reference CIR-on-sigma SV (RP:282-289), full-truncation Euler
 //            Heston and Andersen QE Heston
-// plus the global path index of a local path and the host check of a Sobol
-// index range.
+//   JumpScan Merton jump-diffusion: the log scheme plus compound-Poisson
+//            log-normal jumps (k_sim_jump, k_hedge_oos_jump)
+// plus the global path index of a local path and the host checks of a Sobol
+// index range and of a jump scan's terms and tables.
 #pragma once
 #include "rph_common.h"
 #include "rph_types.h"
@@ -178,6 +180,51 @@ struct SvScan {
   RPH_INLINE Real price() const { return exp(ly); }
 };
 
+// ---------------------------------------------------------------------------
+// Merton jump-diffusion state of one path (SIM_MERTON, JumpTerms): the log
+// scheme of GbmScan with the compensated drift, then the step's jumps.
+// A scan calls count(u) on the step's raw count uniform, draws the jump-size
+// normal zeta only where some lane of the wave jumps (jumps_in_wave: the
+// condition is wave-uniform, and a lane that does not jump never reads zeta)
+// and then step(z, nj, zeta).  The thresholds are kernel arguments, the same
+// for every lane: they stay in scalar registers.
+// ---------------------------------------------------------------------------
+template <typename Real>
+struct JumpScan {
+  Real y;  // log S
+  Real drift, vol, mu_j, sig_j;
+
+  RPH_INLINE void init(const SimDesc& d, const JumpTerms& j) {
+    const Real dt = (Real)d.dt;
+    const Real sdt = sqrt(dt);
+    const Real mu = (Real)d.mu[0], sig = (Real)d.sigma[0];
+    mu_j = (Real)j.mu_j, sig_j = (Real)j.sig_j;
+    const Real kap = expm1(mu_j + (Real)0.5 * sig_j * sig_j);
+    y = log((Real)d.s0[0]);
+    drift = (mu - (Real)0.5 * sig * sig - (Real)j.lam * kap) * dt;  // lam = 0: GbmScan's drift, bit for bit
+    vol = sig * sdt;
+  }
+
+  static RPH_INLINE int count(const JumpTerms& j, uint32_t u) {
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < JUMP_MAX; ++k) n += u >= j.thr[k] ? 1 : 0;
+    return n;
+  }
+
+  static RPH_INLINE bool jumps_in_wave(int nj) { return __any(nj > 0) != 0; }
+
+  RPH_INLINE void step(Real z, int nj, Real zeta) {
+    y += drift + vol * z;  // (GbmScan<SIM_GBM_LOG>::step's statement)
+    if (nj > 0) {
+      const Real fn = (Real)nj;
+      y += fn * mu_j + sqrt(fn) * sig_j * zeta;
+    }
+  }
+
+  RPH_INLINE Real price() const { return exp(y); }
+};
+
 // The Sobol tables hold 30 direction numbers per dimension: point indices are
 // 30-bit.  Past 2^30 the two folds of sobol_point disagree (the aligned one
 // folds gray bits 30 / 31 through the zero columns, the general one stops at
@@ -188,6 +235,23 @@ static constexpr long long SOBOL_INDEX_END = 1LL << 30;
 inline int validate_sobol_range(const char* who, long long first, long long span) {
   if (first < 0 || first >= SOBOL_INDEX_END || span < 0 || span >= SOBOL_INDEX_END - first)
     return rph_report(who, "path range leaves the 30-bit Sobol index space [0, 2^30)");
+  return 0;
+}
+
+// Host check of a SIM_MERTON scan's jump terms and Sobol tables (the scan
+// kernels and the fused out-of-sample kernel).
+inline int validate_jump(const char* who, const SimDesc& s, const JumpTerms* j) {
+  if (!j) return rph_report(who, "SIM_MERTON without JumpTerms");
+  if (s.path_stat != STAT_NONE) return rph_report(who, "SIM_MERTON has no path statistic");
+  if (s.n_fine < 2 || s.reduction < 1) return rph_report(who, "n_fine must be >= 2 and reduction >= 1");
+  if (!s.sv1 || !s.shift1 || s.dims1 < s.n_fine) return rph_report(who, "Sobol table 1 missing or shorter than n_fine");
+  if (!s.sv2 || !s.shift2) return rph_report(who, "SIM_MERTON needs Sobol table 2 (count uniforms, jump-size normals)");
+  if ((long long)s.dims2 < 2LL * s.n_fine) return rph_report(who, "SIM_MERTON: Sobol table 2 shorter than 2 n_fine");
+  if (!(j->lam >= 0.0 && j->lam <= 1e300) || !(j->sig_j >= 0.0 && j->sig_j <= 1e300) || !(fabs(j->mu_j) <= 1e300))
+    return rph_report(who, "JumpTerms: lam >= 0, sig_j >= 0 and mu_j must be finite");
+  for (int k = 0; k < JUMP_MAX; ++k)
+    if (j->thr[k] > (uint32_t)SOBOL_INDEX_END || (k > 0 && j->thr[k] < j->thr[k - 1]))
+      return rph_report(who, "JumpTerms: thresholds must be non-decreasing and at most 2^30");
   return 0;
 }
 

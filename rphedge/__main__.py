@@ -4,7 +4,9 @@
   european   [--paths N] [--parity] [--payoff NAME] ...   European Options notebook driver (NAME: asian_call ...)
              [--exercise bermudan [--exercise-every K]]   ... with the right to exercise at every K-th rebalancing date
   run / european also take the out-of-sample test of the trained hedge:
-             [--oos-paths-log2 M] [--oos-seed S] [--oos-stress key=value ...]   2^M fresh paths (stress: sigma=0.18 ...)
+             [--oos-paths-log2 M] [--oos-seed S] [--oos-stress key=value ...]   2^M fresh paths (stress: sigma=0.18 ...;
+                                                    jumps: jump_intensity=1,jump_mean=-0.1,jump_std=0.15)
+  Merton jump-diffusion: --set model=merton jump_intensity=1 jump_mean=-0.1 jump_std=0.15 (examples/merton_call_30.json)
   run / european also take proportional transaction costs and a no-trade band (RunResult.costs):
              [--cost-rate R] [--rebalance-band B] [--cost-unwind]   a trade of |dh| at S costs R |dh| S
   sts                                                    Single Time Step notebook driver
@@ -49,7 +51,8 @@ def _oos_args(p):
                    help="out-of-sample test of the trained hedge on 2^M fresh paths (0: off)")
     p.add_argument("--oos-seed", type=int, default=None, help="Sobol scramble seed of the test paths")
     p.add_argument("--oos-stress", nargs="*", default=None, metavar="key=value",
-                   help="simulate the test paths under other model parameters (sigma=0.18, xi=0.4 ...)")
+                   help="simulate the test paths under other model parameters (sigma=0.18, xi=0.4 ...; gbm_log / merton: "
+                        "jump_intensity=1,jump_mean=-0.1,jump_std=0.15 makes the test paths jump)")
 
 
 def _cost_args(p):

@@ -8,6 +8,9 @@
   ("Heston stochastic-vol, 30 steps, 1M paths"), which the reference does not
   cover (its SV model is the CIR-on-sigma recursion of
   ``Replicating_Portfolio.py:273-289``).
+* Merton (1976) jump-diffusion: the Poisson-weighted Black-Scholes series for
+  the European price and delta, and the Merton-delta hedge on a run's own grid
+  and paths (with jumps the delta is not the variance-optimal hedge).
 * Hedge anchors on the SAME simulated grid and paths as the learnt hedge
   (self-financing P&L std, the quantity the bench reports):
   Black-Scholes delta (GBM), the Heston delta and the Heston minimum-variance
@@ -433,3 +436,97 @@ def bermudan_tree_price(S0: float, K: float, r: float, sigma: float, T: float, n
                 boundary[i // m] = s[ex].max() if put else s[ex].min()
             v = np.where(ex, x, v)
     return float(v[0]), boundary
+
+
+# ---------------------------------------------------------------------------
+# Merton (1976) jump-diffusion: dS/S = (r - lam kappa) dt + sigma dW + (e^J - 1) dN,
+# J ~ N(mu_j, sig_j^2), kappa = E[e^J] - 1.  Conditional on n jumps the terminal
+# price is lognormal, so the European price is a Poisson-weighted BS series.
+# ---------------------------------------------------------------------------
+def _merton_terms(r: float, sigma: float, tau: float, lam: float, mu_j: float, sig_j: float):
+    """(weights, r_n, sigma_n) of the series over tau: weights Poisson(lam (1 + kappa) tau)."""
+    lk = mu_j + 0.5 * sig_j * sig_j            # log(1 + kappa)
+    kappa = math.expm1(lk)
+    m = lam * (1.0 + kappa) * tau
+    n_terms = int(m + 12.0 * math.sqrt(m) + 30.0) if lam > 0 else 1
+    n = np.arange(n_terms, dtype=np.float64)
+    if m > 0:
+        logw = -m + n * math.log(m) - np.array([math.lgamma(k + 1.0) for k in n])
+        w = np.exp(logw)
+    else:
+        w = (n == 0).astype(np.float64)
+    return w, r - lam * kappa + n * lk / tau, np.sqrt(sigma * sigma + n * sig_j * sig_j / tau)
+
+
+def _merton_price_delta(S0, K, r, sigma, T, lam, mu_j, sig_j, option_type):
+    if not (lam >= 0 and sig_j >= 0 and T > 0):
+        raise ValueError("merton_price: lam >= 0, sig_j >= 0 and T > 0")
+    w, rn, sn = _merton_terms(r, sigma, T, lam, mu_j, sig_j)
+    price = delta = 0.0
+    for wk, rk, sk in zip(w, rn, sn):
+        if wk == 0.0:
+            continue
+        p, d = black_scholes(S0, K, float(rk), float(sk), T, option_type)
+        price += wk * p
+        delta += wk * d
+    return price, delta
+
+
+def merton_price(S0: float, K: float, r: float, sigma: float, T: float, lam: float, mu_j: float, sig_j: float,
+                 option_type: str = "CALL") -> float:
+    """Merton's series price of a European call / put under jump-diffusion
+    (``lam`` jumps per year, log jump N(``mu_j``, ``sig_j``^2)); ``lam = 0`` is Black-Scholes."""
+    return _merton_price_delta(S0, K, r, sigma, T, lam, mu_j, sig_j, option_type)[0]
+
+
+def merton_delta(S0: float, K: float, r: float, sigma: float, T: float, lam: float, mu_j: float, sig_j: float,
+                 option_type: str = "CALL") -> float:
+    """dPrice/dS0 of :func:`merton_price` (the model delta; with jumps NOT the variance-optimal hedge)."""
+    return _merton_price_delta(S0, K, r, sigma, T, lam, mu_j, sig_j, option_type)[1]
+
+
+def merton_delta_hedge(S, bond, strike: float, r: float, sigma: float, T: float, times, lam: float, mu_j: float,
+                       sig_j: float, option_type: str = "CALL", payoff=None, world: int = 1) -> dict:
+    """The Merton-delta hedge on the run's own coarse grid and paths, like
+    :func:`bs_delta_hedge`: wealth starts at the series price, holds the series
+    delta of (t, S_t) and the rest in the bank account; P&L_T = W_T - payoff.
+    With jumps the market is incomplete: this hedge leaves a P&L no
+    rebalancing frequency removes."""
+    import torch
+
+    S = S.double()
+    n_c = S.shape[0]
+    B = torch.as_tensor(np.asarray(bond, np.float64), device=S.device)
+    tt = np.asarray(times, np.float64)
+    put = option_type.upper() != "CALL"
+    if payoff is None:
+        payoff = (strike - S[-1]).clamp_min(0) if put else (S[-1] - strike).clamp_min(0)
+    payoff = payoff.double()
+
+    def price_delta(s, tau):
+        w, rn, sn = _merton_terms(r, sigma, tau, lam, mu_j, sig_j)
+        price, delta = torch.zeros_like(s), torch.zeros_like(s)
+        ls = torch.log(s / strike)
+        for wk, rk, sk in zip(w, rn, sn):
+            if wk < 1e-18:
+                continue
+            sq = float(sk) * math.sqrt(tau)
+            d1 = (ls + (float(rk) + 0.5 * float(sk) ** 2) * tau) / sq
+            Nd1 = 0.5 * torch.erfc(-d1 / math.sqrt(2.0))
+            Nd2 = 0.5 * torch.erfc(-(d1 - sq) / math.sqrt(2.0))
+            f = float(wk)
+            kd = strike * math.exp(-float(rk) * tau)
+            if put:
+                price, delta = price + f * (kd * (1 - Nd2) - s * (1 - Nd1)), delta + f * (Nd1 - 1.0)
+            else:
+                price, delta = price + f * (s * Nd1 - kd * Nd2), delta + f * Nd1
+        return price, delta
+
+    v0, _ = price_delta(S[0], T - tt[0])
+    w = v0.clone()
+    for t in range(n_c - 1):
+        g = float(B[t + 1] / B[t])
+        _, dl = price_delta(S[t], T - tt[t])
+        w = w * g + dl * (S[t + 1] - S[t] * g)
+    pm, ps = _moments(w - payoff, world)
+    return {"price": float(v0.mean()), "pnl_mean": pm, "pnl_std": ps, "n_dates": n_c - 1}

@@ -102,6 +102,7 @@ class HedgeRun:
         # date's fit (None: the paths are whole; flush_sim_ride)
         self.sim_ride = None
         self.kind = self._kind()
+        self._check_jumps()
         self.exercise = self._exercise()
         self.costs = self._costs()
         self.spec = self._spec()
@@ -136,6 +137,40 @@ class HedgeRun:
         if c.payoff == "basket_call" or c.model == "basket":
             return "basket"
         return "pension"
+
+    def _check_jumps(self):
+        """model="merton" (Merton jump-diffusion: the log scheme plus compound-Poisson
+        jumps), validated; the jump keys belong to that model alone."""
+        c = self.cfg
+        lam, mj, sj = (float(c.jump_intensity), float(c.jump_mean), float(c.jump_std))
+        if c.model != "merton":
+            if lam != 0.0 or mj != 0.0 or sj != 0.0:
+                raise ValueError(f"jump_intensity / jump_mean / jump_std need model='merton', got model {c.model!r} "
+                                 f"(a gbm_log hedge meets jumps out of sample: oos_stress)")
+            return
+        self._check_jump_terms(lam, mj, sj, "model='merton'")
+        what = "model='merton' is not available with"
+        if c.payoff in P.PATH_PAYOFFS:
+            raise ValueError(f"{what} the path-dependent payoff {c.payoff!r} (the jump scan keeps no running "
+                             f"statistic of the fine path: call | put)")
+        if self.kind != "european" or c.mortality:
+            raise ValueError(f"{what} a basket, pension or mortality liability (payoff {c.payoff!r}, "
+                             f"mortality={c.mortality}): the jump model simulates one asset for a call | put")
+        if str(c.exercise).lower() != "european":
+            raise ValueError(f"{what} exercise={c.exercise!r} (early exercise under jumps is not supported)")
+        pf = c.parity
+        if pf.complement_head or pf.local_residual_pnl or pf.raw_features:
+            raise ValueError(f"{what} parity=True (the reference has no jump model)")
+
+    def _check_jump_terms(self, lam: float, mj: float, sj: float, what: str):
+        if not (math.isfinite(lam) and lam >= 0):
+            raise ValueError(f"{what}: jump_intensity must be finite and >= 0, got {lam!r}")
+        if not (math.isfinite(sj) and sj >= 0) or not math.isfinite(mj):
+            raise ValueError(f"{what}: jump_std must be finite and >= 0 and jump_mean finite, got {sj!r}, {mj!r}")
+        if lam * float(self.cfg.dt) > 1.0:
+            raise ValueError(f"{what}: jump_intensity * dt = {lam * float(self.cfg.dt):g} > 1 (the scan draws at most "
+                             f"{L.JUMP_MAX} jumps per fine step; up to 1 the mass past that cap is below 1.2e-6 per "
+                             f"step): refine dt")
 
     def _exercise(self) -> Exercise | None:
         """The early-exercise right of the run (None: European), validated."""
@@ -265,7 +300,8 @@ class HedgeRun:
         # LM fits on the GPU, single-asset scans (GBM, SV / Heston): the run's
         # scan and the Gram subsample's go out in ONE launch (k_sim_scan_pair) -
         # the subsample is a few workgroups of pure latency
-        pair = [] if (lm and self.kind == "european" and self.device.type == "cuda") else None
+        # (a Merton scan takes its jump terms beside the descriptor: it is launched plainly)
+        pair = [] if (lm and self.kind == "european" and self.device.type == "cuda" and c.model != "merton") else None
         with self.timer.phase("simulate"):
             p = self._simulate_paths(self.n_local, self.offset, None, into, defer=pair)
             if lm:
@@ -376,7 +412,8 @@ class HedgeRun:
 
         c = self.cfg
         sp = SimpleNamespace(r=c.r, mu=c.mu, sigma=c.sigma, v0=c.v0, s0=c.s0, kappa=c.kappa, theta=c.theta, xi=c.xi,
-                             rho=c.rho)
+                             rho=c.rho, jump_intensity=float(c.jump_intensity), jump_mean=float(c.jump_mean),
+                             jump_std=float(c.jump_std))
         allowed = stress_keys(c.model)
         for k, v in (stress or {}).items():
             if k not in allowed:
@@ -388,6 +425,14 @@ class HedgeRun:
                 sp.v0 = sp.s0 = float(v)
             else:
                 setattr(sp, k, float(v))
+        # the Merton scan simulates a merton run, and a gbm_log run's test paths once the stress makes them jump
+        sp.jumps = c.model == "merton" or sp.jump_intensity > 0
+        if sp.jumps and stress:
+            self._check_jump_terms(sp.jump_intensity, sp.jump_mean, sp.jump_std, "out-of-sample stress")
+            if self.kind != "european" or self.path_stat is not None or self.exercise is not None:
+                raise ValueError("out-of-sample stress: jump_intensity > 0 needs a European call | put on one asset "
+                                 "(the jump scan keeps no path statistic, and early exercise under jumps is not "
+                                 "supported)")
         return sp
 
     def _simulate_paths(self, n: int, offset: int, index_map, into: P.Paths | None, defer: list | None = None,
@@ -413,6 +458,9 @@ class HedgeRun:
                 p = P.simulate_sv(g, n, c.Y, sp.r, sp.v0, model="heston", kappa=sp.kappa, theta=sp.theta, xi=sp.xi,
                                   rho=sp.rho, norm=c.Y, fp64=fp64, scheme=c.heston_scheme,
                                   joint=not c.parity.paired_sobol, seed1=s1, seed2=s2, **kw)
+            elif sp.jumps:
+                p = P.simulate_merton(g, n, c.Y, sp.r, sp.sigma, sp.jump_intensity, sp.jump_mean, sp.jump_std,
+                                      norm=c.Y, fp64=fp64, seed=s1, **kw)
             else:
                 scheme = "arith" if c.model == "gbm" else "log"
                 p = P.simulate_gbm(g, n, c.Y, sp.r, sp.sigma, scheme=scheme, norm=c.Y, fp64=fp64,
@@ -761,7 +809,9 @@ class HedgeRun:
         """The trained hedge on paths it has not seen (:func:`rphedge.oos.out_of_sample`):
         ``2^paths_log2`` fresh paths from Sobol index ``offset`` of the stream
         scrambled with ``seed`` (default :data:`rphedge.oos.OOS_SEED`), optionally
-        simulated under ``stress``-ed model parameters, hedged with the per-date
+        simulated under ``stress``-ed model parameters (``gbm_log`` and ``merton``
+        runs also take ``jump_intensity, jump_mean, jump_std``: with an intensity
+        > 0 the test paths come from the Merton jump scan), hedged with the per-date
         networks, standardisation, strike and bond grid of this run from the
         fitted V0.  Valid after ``run()``, ``replay()`` or ``resume()``.
 
@@ -847,7 +897,18 @@ class HedgeRun:
                         "epochs_mse": [d.fit_mse["epochs"] for d in ind.dates],
                         "terminal_pnl_std": tp["std"], "terminal_residual_std": resid["std"],
                         "self_financing_pnl_std": sf["std"] if sf is not None else None})
-        if self.kind == "european" and self.path_stat is None:
+        if c.model == "merton":
+            from .analytic import merton_delta, merton_delta_hedge, merton_price
+
+            jk = (float(c.jump_intensity), float(c.jump_mean), float(c.jump_std))
+            summary["analytic_price"] = merton_price(c.Y, c.K, c.r, c.sigma, c.T, *jk, c.option_type)
+            summary["analytic_delta"] = merton_delta(c.Y, c.K, c.r, c.sigma, c.T, *jk, c.option_type)
+            # the model-delta hedge on the run's own grid and paths (with jumps not the variance-optimal hedge)
+            md = merton_delta_hedge(self.paths.S, self.paths.bond, float(c.K) / float(c.Y), c.r, c.sigma, float(c.T),
+                                    self.grid.times(), *jk, option_type=c.option_type, payoff=self.v_terminal,
+                                    world=w)
+            summary["merton_delta_pnl_std"] = md["pnl_std"] * scale
+        elif self.kind == "european" and self.path_stat is None:
             from .utils.reports import black_scholes
 
             bs = black_scholes(c.Y, c.K, c.r, c.sigma, c.T, c.option_type)

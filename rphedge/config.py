@@ -184,7 +184,11 @@ class RunConfig:
     heston_scheme: str = "qe"        # qe (Andersen QE, martingale-corrected) | euler (full truncation)
     sv_days_per_year: float = 252.0  # corrected CIR-on-sigma: calibration steps per year (daily data)
     # extensions
-    model: str = "gbm"               # gbm | gbm_log | sv_ref | heston | basket
+    model: str = "gbm"               # gbm | gbm_log | sv_ref | heston | basket | merton (gbm_log + jumps)
+    # Merton jump-diffusion (model="merton"; as oos_stress keys also on a gbm_log run's test paths)
+    jump_intensity: float = 0.0      # jumps per year (>= 0; jump_intensity * dt <= 1)
+    jump_mean: float = 0.0           # mean of the log jump size
+    jump_std: float = 0.0            # std of the log jump size (>= 0)
     payoff: str = "guarantee"        # guarantee | call | put | basket_call | a path-dependent option on one GBM
                                      # asset (ops.paths.PATH_PAYOFFS): asian_call / asian_put, geo_asian_call /
                                      # geo_asian_put, lookback_call / lookback_put (fixed strike K),
@@ -206,7 +210,8 @@ class RunConfig:
     oos_paths_log2: int = 0          # log2 of the fresh test paths (0: off)
     oos_seed: int | None = None      # Sobol scramble seed of the test paths (None: rphedge.oos.OOS_SEED)
     oos_stress: object = None        # simulation-parameter overrides of the test paths: a dict, or "key=value,..."
-                                     # (GBM: sigma, mu / r; Heston: v0, kappa, theta, xi, rho)
+                                     # (GBM: sigma, mu / r; Heston: v0, kappa, theta, xi, rho; gbm_log and merton
+                                     # also jump_intensity, jump_mean, jump_std: test paths that jump)
     mortality: bool = True
     n_assets: int = 1
     basket_weights: tuple = ()

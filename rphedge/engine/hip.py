@@ -798,7 +798,7 @@ class HipBackend(StateBlocks):
 
     def oos(self, sim, snap, data: PnlData, stats, payoff_kind: int, strike: float, has_b: bool = False,
             hold_c: float = 0.0, pnl_out=None, payoff_out=None, costs: Costs | None = None, cost_stats=None,
-            cost_out=None, turn_out=None, trades_out=None):
+            cost_out=None, turn_out=None, trades_out=None, jump=None):
         """Enqueue the fused simulate-and-hedge of fresh paths (one k_hedge_oos
         launch).  ``sim``: the scan's ``SimDesc`` (``ops.paths.gbm_desc`` /
         ``sv_desc``; its output pointers are the optional trace); ``data``: the
@@ -806,8 +806,12 @@ class HipBackend(StateBlocks):
         path tables are not read); ``stats``: ``[num_wgs, EVAL_NSTAT]`` float64 -
         its row count is the grid (``oos_wgs``, or fewer to make workgroups loop).
         ``costs`` and the cost outputs: as in :meth:`pnl` (one k_hedge_oos_cost
-        launch; ``cost_stats`` has the rows of ``stats``)."""
+        launch; ``cost_stats`` has the rows of ``stats``).  ``jump``: the
+        ``JumpTerms`` of a Merton scan (``ops.paths.merton_desc``:
+        k_hedge_oos_jump / k_hedge_oos_jump_cost)."""
         n = self.native
+        if (jump is not None) != (int(sim.model) == L.SIM_MERTON):
+            raise ValueError("oos: jump terms go with a SIM_MERTON scan, and only with one")
         d = n.OosDesc()
         d.sim = sim
         nl = int(sim.n_local)
@@ -828,12 +832,18 @@ class HipBackend(StateBlocks):
         if costs is None:
             if any(t is not None for t in (cost_stats, cost_out, turn_out, trades_out)):
                 raise ValueError("oos: cost outputs without costs")
-            n.oos(d, self.stream)
+            if jump is not None:
+                n.oos_jump(d, jump, self.stream)
+            else:
+                n.oos(d, self.stream)
             return d
         cd = n.CostOosDesc()
         cd.o = d
         self._cost_terms(cd.c, "oos", costs, nl, d.num_wgs, cost_stats, cost_out, turn_out, trades_out)
-        n.oos_cost(cd, self.stream)
+        if jump is not None:
+            n.oos_jump_cost(cd, jump, self.stream)
+        else:
+            n.oos_cost(cd, self.stream)
         return cd
 
     def pnl_finish(self, acc, w0, payoff, carry: float, stats, pnl_out=None):

@@ -15,8 +15,9 @@ Two routes compute it:
   with the run's own scans, form the payoff, call ``backend.pnl``.  Chunks of
   at most ``2^22`` paths bound the memory; their statistics rows are summed.
 * ``fused`` (the MI355X backend, single-asset GBM / GBM + path statistic /
-  Heston with the 8-unit nets): ``k_hedge_oos`` simulates, hedges and scores a
-  path in registers in one launch; nothing of size ``[dates, paths]`` exists.
+  Heston / Merton with the 8-unit nets): ``k_hedge_oos`` (Merton paths, also the
+  jump stress of a ``gbm_log`` run: ``k_hedge_oos_jump``) simulates, hedges and
+  scores a path in registers in one launch; nothing of size ``[dates, paths]`` exists.
 """
 from __future__ import annotations
 
@@ -45,13 +46,16 @@ QUANTILES = (0.01, 0.015, 0.02, 0.05)   # the quantiles collect() reports for th
 
 GBM_STRESS = ("sigma", "mu", "r")
 HESTON_STRESS = ("v0", "kappa", "theta", "xi", "rho")
+JUMP_STRESS = ("jump_intensity", "jump_mean", "jump_std")   # the log scheme only: gbm_log, merton
 
 
 def stress_keys(model: str) -> tuple:
     """The simulation parameters ``stress`` may override for ``model``."""
     if model == "heston":
         return HESTON_STRESS
-    return GBM_STRESS if model in ("gbm", "gbm_log", "basket") else ()
+    if model in ("gbm_log", "merton"):
+        return GBM_STRESS + JUMP_STRESS
+    return GBM_STRESS if model in ("gbm", "basket") else ()
 
 
 def table_seeds(seed: int) -> tuple:
@@ -126,8 +130,8 @@ def fused_unsupported(run) -> str | None:
     c, spec = run.cfg, run.spec
     if run.kind != "european":
         return f"a {run.kind} liability (one simulated asset: call / put or a path-dependent payoff)"
-    if c.model not in ("gbm", "gbm_log", "heston"):
-        return f"model {c.model!r} (gbm | gbm_log | heston)"
+    if c.model not in ("gbm", "gbm_log", "heston", "merton"):
+        return f"model {c.model!r} (gbm | gbm_log | heston | merton)"
     if run.exercise is not None:
         return "early exercise (the stopping rule runs in the materialised scan)"
     if c.dtype != "fp32":
@@ -212,23 +216,27 @@ def payoff_code(run) -> tuple:
 
 
 def _fused_scan(run, n: int, first: int, seeds: tuple, stress, trace: bool):
-    """(Paths | None, SimDesc) of the fused kernel's scan over ``n`` paths from
-    global index ``first``: with ``trace`` the descriptor the run's own scan
-    would launch (deferred, so its coarse tables exist and the kernel fills
-    them), else the same descriptor without any output buffer."""
+    """(Paths | None, SimDesc, JumpTerms | None) of the fused kernel's scan over
+    ``n`` paths from global index ``first``: with ``trace`` the descriptor the
+    run's own scan would launch (deferred, so its coarse tables exist and the
+    kernel fills them), else the same descriptor without any output buffer.
+    The jump terms: a Merton scan's (``model="merton"``, or a jump stress)."""
     c, g = run.cfg, run.grid
     if trace:
         lst = []
         p = run._simulate_paths(n, first, None, None, defer=lst, seeds=seeds, stress=stress)
-        return p, lst[0]
+        return (p,) + (tuple(lst[0]) if isinstance(lst[0], tuple) else (lst[0], None))
     sp = run._sim_params(stress)
+    if sp.jumps:
+        return (None,) + P.merton_desc(g, n, c.Y, sp.r, sp.sigma, sp.jump_intensity, sp.jump_mean, sp.jump_std, c.Y,
+                                       run.device, first, False, seeds[0])
     if c.model == "heston":
         scheme = P.heston_scheme(c.heston_scheme, sp.kappa, sp.xi)
         return None, P.sv_desc(g, n, c.Y, sp.r, sp.v0, "heston", 0.0, 0.0, 0.0, sp.kappa, sp.theta, sp.xi, sp.rho, c.Y,
                                run.device, first, False, False, seeds[0], seeds[1], scheme, 0.0,
-                               not c.parity.paired_sobol)
+                               not c.parity.paired_sobol), None
     return None, P.gbm_desc(g, n, c.Y, sp.r, sp.sigma, "arith" if c.model == "gbm" else "log", c.Y, run.device,
-                            first, False, seeds[0], None, run.path_stat)
+                            first, False, seeds[0], None, run.path_stat), None
 
 
 def resolve_costs(run, costs) -> Costs | None:
@@ -296,19 +304,19 @@ def out_of_sample(run, paths_log2=None, seed=None, offset=0, stress=None, fused=
     if use_fused:
         # one launch: nothing of size [dates, paths] exists unless the paths are asked for
         # (then the kernel's trace fills the buffers of a Paths object)
-        p, sim = _fused_scan(run, n_r, first, seeds, stress, keep_paths)
+        p, sim, jump = _fused_scan(run, n_r, first, seeds, stress, keep_paths)
         data = PnlData(n_dates=nd, features=None, prices=None, bond=ind.pnl_data.bond, fmu=ind.pnl_data.fmu,
                        fisd=ind.pnl_data.fisd, w0=None, wealth0=v0, payoff=None)
         slab = torch.zeros(be.oos_wgs(n_r), L.EVAL_NSTAT, dtype=torch.float64, device=dev)
         kind, strike = payoff_code(run)
         if not cost_only:
-            be.oos(sim, snap, data, slab, kind, strike, has_b=has_b, hold_c=hold_c, pnl_out=pnl)
+            be.oos(sim, snap, data, slab, kind, strike, has_b=has_b, hold_c=hold_c, pnl_out=pnl, jump=jump)
             slabs.append(slab)
         if costs is not None:
             nslab = torch.zeros_like(slab)
             cslab = torch.zeros(slab.shape[0], LC.COST_NSTAT, dtype=torch.float64, device=dev)
             be.oos(sim, snap, data, nslab, kind, strike, has_b=has_b, hold_c=hold_c,
-                   pnl_out=pnl if cost_only else None, costs=costs, cost_stats=cslab)
+                   pnl_out=pnl if cost_only else None, costs=costs, cost_stats=cslab, jump=jump)
             nslabs.append(nslab)
             cslabs.append(cslab)
         if keep_paths:

@@ -69,6 +69,8 @@ HEAD_FREE, HEAD_COMPLEMENT = 0, 1
 LOSS_MSE, LOSS_PINBALL = 0, 1
 
 SIM_GBM_ARITH, SIM_GBM_LOG, SIM_SV_REF, SIM_HESTON, SIM_BASKET, SIM_MORTALITY = range(6)
+SIM_MERTON = 6     # Merton jump-diffusion (JumpTerms; k_sim_jump)
+JUMP_MAX = 8       # JumpTerms.thr: jumps per fine step at most
 HESTON_EULER, HESTON_QE = 0, 1   # SimDesc.scheme (csrc/rph_types.h HestonScheme)
 # SimDesc.path_stat (csrc/rph_types.h PathStat): running statistic of the fine-grid GBM path
 STAT_NONE, STAT_MEAN, STAT_GEOMEAN, STAT_MAX, STAT_MIN = range(5)

@@ -200,6 +200,13 @@ class CostOosDesc(C.Structure):
     _fields_ = [("o", OosDesc), ("c", CostTerms)]
 
 
+class JumpTerms(C.Structure):
+    """The jump terms of a Merton scan (csrc/rph_types.h), a second kernel
+    argument beside ``SimDesc``; ``thr``: ``ops.paths.merton_thresholds(lam * dt)``."""
+
+    _fields_ = [("lam", C.c_double), ("mu_j", C.c_double), ("sig_j", C.c_double), ("thr", C.c_uint32 * L.JUMP_MAX)]
+
+
 DESCRIPTORS = (TrainDesc, EvalDesc, PnlFinishDesc, PnlDesc, LmDpDesc, LmDesc, SimDesc)
 # descriptors of the native library's second field table (csrc/rph_layout.h
 # RPH_DESCRIPTORS_EXT, rph_layout_fields_ext): checked by name at load like the first
@@ -213,6 +220,9 @@ DESCRIPTORS_SIM = (SimRideDesc,)
 # transaction costs; the table also holds the rows of the embedded CostTerms,
 # and has constants of its own (rph_layout_consts_cost, ops/layout_cost.py)
 DESCRIPTORS_COST = (CostPnlDesc, CostOosDesc)
+
+# ... and its sixth (RPH_DESCRIPTORS_JUMP, rph_layout_fields_jump): the Merton jump scans
+DESCRIPTORS_JUMP = (JumpTerms,)
 
 # upper-case ints of layout.py that the native table does not hold (Python only)
 PYTHON_ONLY: tuple[str, ...] = ()
@@ -253,6 +263,13 @@ def native_layout_sim(lib) -> list[tuple[str, str, int, int]]:
     """The library's fourth field table: the rows of :data:`DESCRIPTORS_SIM`."""
     fr = C.POINTER(_FieldRow)()
     nf = lib.rph_layout_fields_sim(C.byref(fr))
+    return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
+
+
+def native_layout_jump(lib) -> list[tuple[str, str, int, int]]:
+    """The library's sixth field table: the rows of :data:`DESCRIPTORS_JUMP`."""
+    fr = C.POINTER(_FieldRow)()
+    nf = lib.rph_layout_fields_jump(C.byref(fr))
     return [(r.strct.decode(), r.field.decode(), r.offset, r.size) for r in fr[:nf]]
 
 
@@ -299,6 +316,13 @@ def _bind(lib):
         "rph_layout_fields_sim": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_fields_cost": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
         "rph_layout_consts_cost": (C.c_int, [C.POINTER(C.POINTER(_ConstRow))]),
+        "rph_layout_fields_jump": (C.c_int, [C.POINTER(C.POINTER(_FieldRow))]),
+        "rph_simulate_jump": (C.c_int, [C.POINTER(SimDesc), C.POINTER(JumpTerms), VP]),
+        "rph_simulate_jump_check": (C.c_int, [C.POINTER(SimDesc), C.POINTER(JumpTerms)]),
+        "rph_oos_jump": (C.c_int, [C.POINTER(OosDesc), C.POINTER(JumpTerms), VP]),
+        "rph_oos_jump_check": (C.c_int, [C.POINTER(OosDesc), C.POINTER(JumpTerms)]),
+        "rph_oos_jump_cost": (C.c_int, [C.POINTER(CostOosDesc), C.POINTER(JumpTerms), VP]),
+        "rph_oos_jump_cost_check": (C.c_int, [C.POINTER(CostOosDesc), C.POINTER(JumpTerms)]),
         "rph_pnl_cost": (C.c_int, [C.POINTER(CostPnlDesc), VP]),
         "rph_pnl_cost_check": (C.c_int, [C.POINTER(CostPnlDesc)]),
         "rph_oos_cost": (C.c_int, [C.POINTER(CostOosDesc), VP]),
@@ -393,8 +417,9 @@ def load(required: bool | None = None):
         lib = C.CDLL(str(_LIB_PATH), mode=C.RTLD_GLOBAL)
         _bind(lib)
         fields, consts = native_layout(lib)
-        bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib) + native_layout_sim(lib),
-                                consts, classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE + DESCRIPTORS_SIM)
+        bad = layout_mismatches(fields + native_layout_ext(lib) + native_layout_ride(lib) + native_layout_sim(lib)
+                                + native_layout_jump(lib), consts,
+                                classes=DESCRIPTORS + DESCRIPTORS_EXT + DESCRIPTORS_RIDE + DESCRIPTORS_SIM + DESCRIPTORS_JUMP)
         cfields, cconsts = native_layout_cost(lib)
         bad += layout_mismatches(cfields, cconsts, classes=(CostTerms,) + DESCRIPTORS_COST, layout=LC)
         if bad:
@@ -469,6 +494,20 @@ def simulate_check(desc: SimDesc):
     """The descriptor checks of :func:`simulate` alone: raises as it would, launches nothing."""
     lib = load(required=True)
     _check(lib.rph_simulate_check(C.byref(desc)), "rph_simulate")
+
+
+def simulate_jump(desc: SimDesc, jump: JumpTerms, stream=None):
+    """The Merton jump-diffusion scan (k_sim_jump): ``desc.model`` SIM_MERTON, ``jump`` its jump terms."""
+    lib = load(required=True)
+    _check(lib.rph_simulate_jump(C.byref(desc), C.byref(jump) if jump is not None else None, stream_handle(stream)),
+           "rph_simulate_jump")
+
+
+def simulate_jump_check(desc: SimDesc, jump: JumpTerms):
+    """The descriptor checks of :func:`simulate_jump` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_simulate_jump_check(C.byref(desc), C.byref(jump) if jump is not None else None),
+           "rph_simulate_jump")
 
 
 def sobol_normal_check(n: int, offset: int = 0):
@@ -687,6 +726,24 @@ def oos_check(desc: OosDesc):
     """The descriptor checks of :func:`oos` alone: raises as it would, launches nothing."""
     lib = load(required=True)
     _check(lib.rph_oos_check(C.byref(desc)), "rph_oos")
+
+
+def oos_jump(desc: OosDesc, jump: JumpTerms, stream=None):
+    """Fused simulate-and-hedge on Merton jump-diffusion paths (k_hedge_oos_jump)."""
+    load(required=True)
+    _check(_lib.rph_oos_jump(C.byref(desc), C.byref(jump), stream_handle(stream)), "rph_oos_jump")
+
+
+def oos_jump_check(desc: OosDesc, jump: JumpTerms):
+    """The descriptor checks of :func:`oos_jump` alone: raises as it would, launches nothing."""
+    lib = load(required=True)
+    _check(lib.rph_oos_jump_check(C.byref(desc), C.byref(jump)), "rph_oos_jump")
+
+
+def oos_jump_cost(desc: CostOosDesc, jump: JumpTerms, stream=None):
+    """... under transaction costs (k_hedge_oos_jump_cost)."""
+    load(required=True)
+    _check(_lib.rph_oos_jump_cost(C.byref(desc), C.byref(jump), stream_handle(stream)), "rph_oos_jump_cost")
 
 
 def oos_max_wgs() -> int:

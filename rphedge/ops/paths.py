@@ -247,6 +247,104 @@ def simulate_gbm(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, s
     return p
 
 
+def merton_thresholds(lam_dt: float) -> np.ndarray:
+    """The jump-count thresholds of one fine step of the Merton scan:
+    ``T_k = min(floor(F_k 2^30), 2^30)``, ``F_k`` the Poisson(``lam_dt``) CDF by
+    the recurrence ``f_0 = exp(-lam_dt)``, ``f_{k+1} = f_k lam_dt / (k + 1)`` in
+    fp64.  The step's count is ``#{k < JUMP_MAX : u >= T_k}`` of its raw 30-bit
+    Sobol integer ``u`` - an integer comparison, so the kernel (``JumpTerms.thr``)
+    and the numpy twin count the same jumps.  ``lam_dt = 0``: every ``T_k`` is
+    ``2^30`` (no jump)."""
+    lam_dt = float(lam_dt)
+    if not (0.0 <= lam_dt < math.inf):
+        raise ValueError(f"merton_thresholds: lam * dt must be finite and >= 0, got {lam_dt!r}")
+    thr = np.empty(L.JUMP_MAX, dtype=np.uint32)
+    f = math.exp(-lam_dt)
+    F = f
+    for k in range(L.JUMP_MAX):
+        thr[k] = min(int(math.floor(F * 2.0 ** 30)), 1 << 30)
+        f = f * lam_dt / (k + 1)
+        F = F + f
+    return thr
+
+
+def merton_counts(u: np.ndarray, thr: np.ndarray) -> np.ndarray:
+    """Jump counts of the raw 30-bit count uniforms ``u`` (any shape) under ``merton_thresholds``."""
+    u = np.asarray(u, dtype=np.int64)
+    return (u[..., None] >= np.asarray(thr, dtype=np.int64)).sum(axis=-1)
+
+
+def jump_compensator(lam: float, mu_j: float, sig_j: float) -> float:
+    """``lam * kappa``, ``kappa = E[e^J] - 1``: the drift the jumps add, taken off the diffusion's."""
+    return float(lam) * math.expm1(float(mu_j) + 0.5 * float(sig_j) ** 2)
+
+
+def _check_jump_terms(lam: float, mu_j: float, sig_j: float):
+    if not (lam >= 0 and math.isfinite(lam)):
+        raise ValueError(f"jump_intensity must be finite and >= 0, got {lam!r}")
+    if not (sig_j >= 0 and math.isfinite(sig_j)) or not math.isfinite(mu_j):
+        raise ValueError(f"jump_std must be finite and >= 0 and jump_mean finite, got {sig_j!r}, {mu_j!r}")
+
+
+def merton_desc(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, lam: float, mu_j: float, sig_j: float,
+                norm: float, dev, offset: int = 0, fp64: bool = False, seed: int = SEED_W1, index_map=None):
+    """(SimDesc, JumpTerms) of the Merton scan without output buffers.  All
+    three shocks come from ONE scrambled Sobol sequence of 3 n_fine dimensions:
+    table 1 = the diffusion normals [0, nf), table 2 = the count uniforms
+    [nf, 2 nf) and the jump-size normals [2 nf, 3 nf)."""
+    from . import native
+
+    _check_jump_terms(lam, mu_j, sig_j)
+    nf = grid.n_fine
+    sv, sh, _ = device_table(3 * nf, seed, dev)
+    d = _desc(L.SIM_MERTON, n_local, offset, grid, fp64, False, index_map)
+    d.sv1, d.shift1, d.dims1 = sv.data_ptr(), sh.data_ptr(), nf
+    d.sv2, d.shift2, d.dims2 = sv.data_ptr() + nf * 32 * 4, sh.data_ptr() + nf * 4, 2 * nf
+    d.s0[0], d.mu[0], d.sigma[0], d.inv_norm[0] = s0, mu, sigma, 1.0 / norm
+    j = native.JumpTerms()
+    j.lam, j.mu_j, j.sig_j = float(lam), float(mu_j), float(sig_j)
+    for k, t in enumerate(merton_thresholds(lam * grid.dt)):
+        j.thr[k] = int(t)
+    return d, j
+
+
+def simulate_merton(grid: Grid, n_local: int, s0: float, mu: float, sigma: float, lam: float, mu_j: float,
+                    sig_j: float, norm: float = 1.0, device="cuda", offset: int = 0, fp64: bool = False,
+                    seed: int = SEED_W1, stream=None, out: Paths | None = None, index_map=None,
+                    defer: list | None = None) -> Paths:
+    """Merton jump-diffusion on the fine grid, stored on the coarse grid
+    (k_sim_jump; on a CPU device the fp64 twin :func:`_cpu_merton`): log-Euler
+    GBM with the compensated drift ``(mu - sigma^2/2 - lam kappa) dt`` plus, per
+    fine step, ``N ~ Poisson(lam dt)`` (at most ``JUMP_MAX``) log-normal jumps
+    ``N mu_j + sqrt(N) sig_j zeta``.  ``out``, ``index_map``: as in
+    :func:`simulate_gbm`; ``defer`` (GPU only): append ``(SimDesc, JumpTerms)``
+    to that list instead of launching.  Returns paths of kind "gbm", one
+    feature S."""
+    dev = torch.device(device)
+    S = out.S if out is not None else torch.empty(grid.n_coarse, n_local, dtype=torch.float32, device=dev)
+    fin = out.S_final if out is not None else torch.empty(n_local, dtype=torch.float32, device=dev)
+    if _dev_is_gpu(dev):
+        from . import native
+
+        d, j = merton_desc(grid, n_local, s0, mu, sigma, lam, mu_j, sig_j, norm, dev, offset, fp64, seed, index_map)
+        d.out, d.final_out = S.data_ptr(), fin.data_ptr()
+        if defer is not None:
+            defer.append((d, j))
+        else:
+            native.simulate_jump(d, j, stream)
+    else:
+        s_np, f_np = _cpu_merton(grid, n_local, s0, mu, sigma, lam, mu_j, sig_j, offset, seed, index_map)
+        S.copy_(torch.from_numpy((s_np / norm).astype(np.float32)))
+        fin.copy_(torch.from_numpy((f_np / norm).astype(np.float32)))
+    if out is not None:
+        return out
+    p = Paths(kind="gbm", grid=grid, n_local=n_local, path_offset=offset, S=S, bond=grid.bond(0.0), S_final=fin,
+              norm=norm)
+    p.meta["index_map"] = index_map
+    p.meta["jumps"] = (float(lam), float(mu_j), float(sig_j))
+    return p
+
+
 def simulate_sv(grid: Grid, n_local: int, s0: float, mu: float, v0: float, model: str = "sv_ref",
                 a=0.0, b=0.0, c=0.0, kappa=0.0, theta=0.0, xi=0.0, rho=0.0, norm: float = 1.0,
                 device="cuda", offset: int = 0, fp64: bool = False, parity_nan: bool = False,
@@ -489,6 +587,32 @@ def _cpu_gbm(grid, n, s0, mu, sigma, scheme, offset, seed, index_map=None, path_
     if path_stat is None:
         return out, fin
     return out, fin, aout, stat
+
+
+def _cpu_merton(grid, n, s0, mu, sigma, lam, mu_j, sig_j, offset, seed, index_map=None, counts: list | None = None):
+    """fp64 twin of k_sim_jump: (S coarse, S final).  One Sobol sequence of
+    3 n_fine dimensions: diffusion normals, count uniforms, jump-size normals.
+    ``counts``: a list that receives the jump counts ``[n, n_fine]`` (column 0 unused)."""
+    _check_jump_terms(lam, mu_j, sig_j)
+    nf = grid.n_fine
+    X = _u30(3 * nf, seed, n, offset, 3 * nf, index_map)
+    W = ndtri_u30_f64(X[:, :nf])
+    N = merton_counts(X[:, nf:2 * nf], merton_thresholds(lam * grid.dt))
+    with np.errstate(invalid="ignore"):
+        Z = np.where(N > 0, ndtri_u30_f64(X[:, 2 * nf:]), 0.0)
+    if counts is not None:
+        counts.append(N)
+    dt = grid.dt
+    drift = (mu - 0.5 * sigma ** 2 - jump_compensator(lam, mu_j, sig_j)) * dt
+    y = np.full(n, math.log(s0), dtype=np.float64)
+    out = np.empty((grid.n_coarse, n))
+    out[0] = s0
+    for t in range(1, nf):
+        y = y + drift + sigma * math.sqrt(dt) * W[:, t]
+        y = y + np.where(N[:, t] > 0, N[:, t] * mu_j + np.sqrt(N[:, t]) * sig_j * Z[:, t], 0.0)
+        if t % grid.reduction == 0 and t // grid.reduction < grid.n_coarse:
+            out[t // grid.reduction] = np.exp(y)
+    return out, np.exp(y)
 
 
 def _u30(table_dims, seed, n_local, offset, dims, index_map=None):

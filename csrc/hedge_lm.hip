@@ -436,7 +436,15 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
   constexpr int NG = LS::NBLK * 1024;
   __shared__ double part[1024];
   const int inst = blockIdx.y;  // multi-start instance
-  if (pass > 0 && lm.state[(size_t)inst * LMS_FLOATS + LMS_SLOTS + LM_SLOT * (pass & 1) + LSS_STOP] != 0.0) return;
+  // The stop flag of an adaptive budget (a stopped launch writes nothing and
+  // exchanges nothing) is non-zero only in a fit with lm.stop_tol > 0: read
+  // only there, and then issued here with nothing waiting for it - every
+  // branch below tests it after its slab loads (always valid memory), before
+  // its first store to red and before the exchange, so the flag's round trip
+  // is the slabs' and not one in front of them
+  double stop_flag = 0.0;
+  if (pass > 0 && lm.stop_tol > 0.f)
+    stop_flag = lm.state[(size_t)inst * LMS_FLOATS + LMS_SLOTS + LM_SLOT * (pass & 1) + LSS_STOP];
   // fused data-parallel exchange: the sequence number the pass kernel advanced
   const unsigned seq = lm.dp_fused ? __hip_atomic_load(lm.dp.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   red += (size_t)inst * LM_RED;
@@ -445,6 +453,11 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
   const int tid = threadIdx.x;
   // (wg0: the final evaluation's launch starts past the Gram workgroups)
   const int bx = (int)blockIdx.x + wg0;
+  // Every slab load below is unconditional, its row clamped to the last one,
+  // and the rows past the grid are dropped by a select afterwards: a load
+  // under a condition is compiled as a branch with its own wait, and a thread's
+  // 4 to 16 rows then cost as many round trips in a row instead of one
+  const int last_row = max(lm.num_wgs - 1, 0), last_slab = max(lm.gram_wgs - 1, 0);
   const int NGW = lm_gram_red_wgs(NG, lm.gram_wgs);       // Gram workgroups
   const int NPW = lm_pk_red_wgs(R, lm.num_wgs, lm.dp_fused);  // packet workgroups
   if (bx >= NGW + NPW) {
@@ -453,7 +466,7 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     const bool og_pass = lm.out_gram && pass > lm.passes - LM_OUTG_TAIL;
     const int ob = bx - (NGW + NPW);
     if (!og_pass) {
-      if (ob == 0 && tid == 0) red[LM_RED_OUTG] = -1.0;
+      if (ob == 0 && tid == 0 && stop_flag == 0.0) red[LM_RED_OUTG] = -1.0;
       return;
     }
     constexpr int NPK = NU * (NU + 1) / 2;
@@ -484,22 +497,23 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
       double v;
       if (lm.num_wgs > 256) {
         // (<= 512 rows: rows 32 w + 8 k + [0, 8), the same tree one level deeper)
+        float x[8];
         double r[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int row = 32 * w + 8 * k + u;
-          r[u] = (e < NPK && row < lm.num_wgs) ? (double)so[(size_t)row * 3 * 1024] : 0.0;
-        }
+        for (int u = 0; u < 8; ++u) x[u] = so[(size_t)min(32 * w + 8 * k + u, last_row) * 3 * 1024];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r[u] = (e < NPK && 32 * w + 8 * k + u < lm.num_wgs) ? (double)x[u] : 0.0;
         v = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
       } else {
+        float x[4];
         double r[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int row = 16 * w + 4 * k + u;
-          r[u] = (e < NPK && row < lm.num_wgs) ? (double)so[(size_t)row * 3 * 1024] : 0.0;
-        }
+        for (int u = 0; u < 4; ++u) x[u] = so[(size_t)min(16 * w + 4 * k + u, last_row) * 3 * 1024];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) r[u] = (e < NPK && 16 * w + 4 * k + u < lm.num_wgs) ? (double)x[u] : 0.0;
         v = (r[0] + r[1]) + (r[2] + r[3]);
       }
+      if (stop_flag != 0.0) return;
       v += __shfl_xor(v, 16, 64);
       v += __shfl_xor(v, 32, 64);
       if (k == 0) part[w * 16 + le] = v;
@@ -541,11 +555,17 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     double h[2];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
+      float x[16] = {};
       double r[16];
+      // (wave-uniform: the second half has rows only in the 32-row form)
+      if (hh == 0 || RPG == 32) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x[u] = slab_o[(size_t)min(RPG * g + 16 * hh + u, last_row) * 3 * 1024];
+      }
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int w = RPG * g + 16 * hh + u;
-        r[u] = (e < NPK && w < lm.num_wgs && (hh == 0 || RPG == 32)) ? (double)slab_o[(size_t)w * 3 * 1024] : 0.0;
+        r[u] = (e < NPK && w < lm.num_wgs && (hh == 0 || RPG == 32)) ? (double)x[u] : 0.0;
       }
 #pragma unroll
       for (int st = 1; st < 16; st <<= 1)
@@ -553,6 +573,7 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
         for (int u = 0; u < 16; u += 2 * st) r[u] += r[u + st];
       h[hh] = r[0];
     }
+    if (stop_flag != 0.0) return;
     part[tid] = RPG == 32 ? h[0] + h[1] : h[0];
     __syncthreads();
     if (g == 0) {
@@ -592,14 +613,18 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     // combined in the LDS form's order: even groups, odd groups, their sum
     const int e = bx * 1024 + tid;
     const float* col = slab_g + e;
+    float x[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) x[q] = col[(size_t)min(q, last_slab) * NG];
     double a = 0.0, b = 0.0;
 #pragma unroll
     for (int q = 0; q < 16; q += 2) {
-      const double p0 = q < lm.gram_wgs ? (0.0 + (double)col[(size_t)q * NG]) + 0.0 : 0.0 + 0.0;
-      const double p1 = q + 1 < lm.gram_wgs ? (0.0 + (double)col[(size_t)(q + 1) * NG]) + 0.0 : 0.0 + 0.0;
+      const double p0 = q < lm.gram_wgs ? (0.0 + (double)x[q]) + 0.0 : 0.0 + 0.0;
+      const double p1 = q + 1 < lm.gram_wgs ? (0.0 + (double)x[q + 1]) + 0.0 : 0.0 + 0.0;
       a += p0;
       b += p1;
     }
+    if (stop_flag != 0.0) return;
     const double v = (a + b) * (double)lm.inv_ns;
     red[e] = v;
     tpack(e, v);
@@ -613,13 +638,18 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     const int l = tid & 63, g = tid >> 6;
     const int e = bx * 64 + l;
     const float* col = slab_g + e;
+    // (s0: slabs g, g + 32, ..., s1: slabs g + 16, g + 48, ..., each in rising order)
     double s0 = 0.0, s1 = 0.0;
-    int w = g;
-    for (; w + 16 < lm.gram_wgs; w += 32) {
-      s0 += (double)col[(size_t)w * NG];
-      s1 += (double)col[(size_t)(w + 16) * NG];
+    for (int w = g; w < lm.gram_wgs; w += 64) {
+      float x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[u] = col[(size_t)min(w + 16 * u, last_slab) * NG];
+      s0 += (double)x[0];
+      if (w + 16 < lm.gram_wgs) s1 += (double)x[1];
+      if (w + 32 < lm.gram_wgs) s0 += (double)x[2];
+      if (w + 48 < lm.gram_wgs) s1 += (double)x[3];
     }
-    if (w < lm.gram_wgs) s0 += (double)col[(size_t)w * NG];
+    if (stop_flag != 0.0) return;
     part[tid] = s0 + s1;
     __syncthreads();
     if (g == 0) {
@@ -648,12 +678,17 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     // the all-zero rest (the same adds, so the same bits)
     const int i = tid;
     if (i < P + 4) {
+      float x[16];
       double a[16];
+#pragma unroll
+      for (int p = 0; p < 16; ++p)
+        x[p] = slab_b[(size_t)min((int)(__builtin_bitreverse32((unsigned)p) >> 28), last_row) * R + i];
 #pragma unroll
       for (int p = 0; p < 16; ++p) {
         const int r = (int)(__builtin_bitreverse32((unsigned)p) >> 28);
-        a[p] = r < lm.num_wgs ? (double)slab_b[(size_t)r * R + i] : 0.0;
+        a[p] = r < lm.num_wgs ? (double)x[p] : 0.0;
       }
+      if (stop_flag != 0.0) return;
 #pragma unroll
       for (int st = 8; st >= 1; st >>= 1)
 #pragma unroll
@@ -670,7 +705,9 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
     const int k = tid & 31, q = tid >> 5;
     const int i = pw * 32 + k;
     const int row = (int)(__builtin_bitreverse32((unsigned)q) >> 27);
-    part[tid] = row < lm.num_wgs ? (double)slab_b[(size_t)row * R + i] : 0.0;
+    const double v = row < lm.num_wgs ? (double)slab_b[(size_t)row * R + i] : 0.0;
+    if (stop_flag != 0.0) return;
+    part[tid] = v;
     __syncthreads();
 #pragma unroll
     for (int st = 16; st >= 1; st >>= 1) {
@@ -684,17 +721,21 @@ __global__ __launch_bounds__(1024) void k_lm_reduce(const LmDesc lm, double* __r
   const int k = tid & 3, grp = tid >> 2;
   const int i = pw * 4 + k;
   const int row = (int)(__builtin_bitreverse32((unsigned)grp) >> 24);
+  double v0;
   if (lm.num_wgs > 256) {
     // (<= 512 rows: position grp holds rows bitrev9(grp) = 2 bitrev8(grp) and
     // bitrev9(grp + 256) = 2 bitrev8(grp) + 1 - the first level of the
     // contiguous-halves tree over 512 rows; the LDS tree below is the rest)
     const int r0 = 2 * row;
-    const double a = r0 < lm.num_wgs ? (double)slab_b[(size_t)r0 * R + i] : 0.0;
-    const double b = r0 + 1 < lm.num_wgs ? (double)slab_b[(size_t)(r0 + 1) * R + i] : 0.0;
-    part[tid] = a + b;
+    const float xa = slab_b[(size_t)min(r0, last_row) * R + i], xb = slab_b[(size_t)min(r0 + 1, last_row) * R + i];
+    const double a = r0 < lm.num_wgs ? (double)xa : 0.0;
+    const double b = r0 + 1 < lm.num_wgs ? (double)xb : 0.0;
+    v0 = a + b;
   } else {
-    part[tid] = row < lm.num_wgs ? (double)slab_b[(size_t)row * R + i] : 0.0;
+    v0 = row < lm.num_wgs ? (double)slab_b[(size_t)row * R + i] : 0.0;
   }
+  if (stop_flag != 0.0) return;
+  part[tid] = v0;
   __syncthreads();
 #pragma unroll
   for (int st = 128; st >= 1; st >>= 1) {
